@@ -20,9 +20,15 @@ Graph500 R-MAT, configs[3]; --scale 22 by default), arxiv (configs[2]),
 backbone (configs[4]), exact_er (the dense exact scorer, Cora size by
 default, --xer-n for a Roman-like graph of that size; replicas at N > 1).
 
-Prints ONE JSON line (rank 0) with roofline (dominant kernel, HIP events on
-the library's stream) and cpu_baseline (the oracle's NumPy/SciPy restatement
-of the reference path, bounded sample, timed on this host, rank 0 at N=1).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line
+(rank 0): metric, value, ms_per_step and the configuration.  --dump-outputs DIR
+also writes the arrays the last timed step returned as DIR/<name>.npy.
+
+--full adds, to the same line, what takes work of its own: roofline and kernels
+(dominant kernel, HIP events on the library's stream during the timed steps),
+the steps timed again in this host's default OpenBLAS order, the drop-in tie
+rule's cost, and cpu_baseline (the oracle's NumPy/SciPy restatement of the
+reference path, bounded sample, timed on this host, rank 0 at N=1).
 """
 
 from __future__ import annotations
@@ -63,10 +69,6 @@ PMC_KERNEL = {"cg_res": "gs::k_cg_resident<", "cg_reg": "gs::k_cg_reg", "cg_pq":
 PMC_FIRST_CALL = {"jaccard": ("k_jac_plan", "k_jac_mask", "k_jac_emit", "k_jac_bytes")}
 
 
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from provenance import source_hash  # noqa: E402
-
-SRC_HASH = source_hash()
 CU_COUNT, CLOCK_GHZ = 256, 2.4  # MI355X (MI355X_MICROARCH.md): issue-rate peaks below
 
 
@@ -77,6 +79,10 @@ def pmc_summary(workload: str):
     are never joined to this run's timings.  Returns (summary, file, note)."""
     import glob
 
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from provenance import source_hash
+
+    SRC_HASH = source_hash()
     files = sorted(glob.glob(os.path.join(ROOT, "profiles", f"*_{workload}_pmc_summary.json")))
     stale = None
     for f in reversed(files):
@@ -246,6 +252,31 @@ def emit(result):
     if isinstance(result.get("cpu_baseline"), dict):
         result["cpu_baseline"]["host"] = host_info()
     print(json.dumps(result), flush=True)
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes over all arrays of one --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: the arrays the timed path returned in its last step, one
+    DIR/<name>.npy each, float64 or float32 (masks and counts as float32 / float64).
+    An array above its equal share of DUMP_BUDGET is cut to a fixed sample: the sorted
+    flat positions default_rng(0) draws for that size, the same in every run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = DUMP_BUDGET // max(1, len(arrays))
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        if a.nbytes > share:
+            pick = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False,
+                                                   shuffle=False)
+            pick.sort()
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def host_cores() -> int:
@@ -545,8 +576,9 @@ def bench_backbone(args, world, rank, local_rank, dev, dist):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    ctx.profile(True)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile(True)
+        ctx.profile_reset()
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -557,14 +589,18 @@ def bench_backbone(args, world, rank, local_rank, dev, dist):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    prof = ctx.profile_read()
-    ctx.profile(False)
+    prof = None
+    if args.full:
+        prof = ctx.profile_read()
+        ctx.profile(False)
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if dist.get_backend() != "nccl":
             t = t.cpu()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"keep_mask": out})
     kept = int((out != 0).sum().item())
     roofline = None
     if prof and "metric_backbone" in prof:
@@ -584,7 +620,7 @@ def bench_backbone(args, world, rank, local_rank, dev, dist):
                    "graph_gen_s": round(t_gen, 2)},
         "roofline": roofline,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_backbone(ei, n, cost)
     if rank == 0:
         emit(result)
@@ -648,8 +684,9 @@ def bench_topology(args, world, rank, local_rank, dev, dist):
     for _ in range(args.warmup):
         res = compute_topology_metrics(A)
     torch.cuda.synchronize(dev)
-    ctx.profile(True)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile(True)
+        ctx.profile_reset()
     if dist:
         dist.barrier()
     t0 = time.perf_counter()
@@ -659,8 +696,12 @@ def bench_topology(args, world, rank, local_rank, dev, dist):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    prof = ctx.profile_read()
-    ctx.profile(False)
+    prof = None
+    if args.full:
+        prof = ctx.profile_read()
+        ctx.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: np.float64(v) for k, v in res.items()})
     roofline = None
     if prof and "exact_er_dgemm" in prof:
         p = prof["exact_er_dgemm"]
@@ -685,7 +726,7 @@ def bench_topology(args, world, rank, local_rank, dev, dist):
                               for k, v in res.items()}},
         "roofline": roofline,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import gsparse_oracle as O
 
@@ -747,6 +788,11 @@ def bench_geodesic(args, world, rank, local_rank, dev, dist):
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     a, b = res
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     {"preservation_ratio": np.float64(a["preservation_ratio"]),
+                      "violations": np.float64(b["violations"]),
+                      "unreachable_backbone": np.float64(b["unreachable_backbone"])})
     result = {
         "metric": "geodesic-check calls/sec (compute_geodesic_preservation + verify_geodesic_preservation)",
         "value": round(world * args.steps / elapsed, 3), "unit": "calls/s", "n_gpus": world,
@@ -762,7 +808,7 @@ def bench_geodesic(args, world, rank, local_rank, dev, dist):
                               "unreachable_backbone": int(b["unreachable_backbone"])}},
         "roofline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import gsparse_oracle as O
 
@@ -817,8 +863,9 @@ def bench_exact_er(args, world, rank, local_rank, dev, dist):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    ctx.profile(True)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile(True)
+        ctx.profile_reset()
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -829,14 +876,18 @@ def bench_exact_er(args, world, rank, local_rank, dev, dist):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    prof = ctx.profile_read()
-    ctx.profile(False)
+    prof = None
+    if args.full:
+        prof = ctx.profile_read()
+        ctx.profile(False)
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if dist.get_backend() != "nccl":
             t = t.cpu()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"exact_er": out})
     roofline = None
     if prof and "exact_er_dgemm" in prof:
         p = prof["exact_er_dgemm"]
@@ -872,7 +923,7 @@ def bench_exact_er(args, world, rank, local_rank, dev, dist):
                    "parallelism": f"{world} replicas" if world > 1 else "1 GPU"},
         "roofline": roofline,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_exact_er(a.indptr, a.indices, a.data, n)
     if rank == 0:
         emit(result)
@@ -919,8 +970,9 @@ def bench_scorers(args, world, rank, local_rank, dev, dist):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    ctx.profile(True)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile(True)
+        ctx.profile_reset()
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -931,33 +983,41 @@ def bench_scorers(args, world, rank, local_rank, dev, dist):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    prof = ctx.profile_read()
-    ctx.profile(False)
-    # SURVEY 8(d) algorithmic bytes (binarised degrees; the graph is symmetric)
-    deg = np.diff(indptr).astype(np.float64)
-    rows = np.repeat(np.arange(n), np.diff(indptr))
-    b_j = 4.0 * float(np.sum(deg[rows] + deg[indices])) + 12.0 * nnz
-    b_aa = b_j + 8.0 * float(np.sum(eng.common_neighbors()))
-    b_f = 2.0 * f * 4 * nnz + 8.0 * nnz + 3.0 * n * f * 4
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("jaccard", "adamic_adar", "feature_cosine",
+                                                  "approx_er"), outs)))
+    extra = {}
+    if args.full:
+        prof = ctx.profile_read()
+        ctx.profile(False)
+        # SURVEY 8(d) algorithmic bytes (binarised degrees; the graph is symmetric)
+        deg = np.diff(indptr).astype(np.float64)
+        rows = np.repeat(np.arange(n), np.diff(indptr))
+        b_j = 4.0 * float(np.sum(deg[rows] + deg[indices])) + 12.0 * nnz
+        b_aa = b_j + 8.0 * float(np.sum(eng.common_neighbors()))
+        b_f = 2.0 * f * 4 * nnz + 8.0 * nnz + 3.0 * n * f * 4
 
-    def roof(names, by):
-        ms = sum(prof[nm]["ms"] for nm in names if nm in prof)
-        la = max((prof[nm]["launches"] for nm in names if nm in prof), default=0)
-        if not la or ms <= 0:
-            return None
-        avg = ms / la
-        ach = by / (avg * 1e-3) / 1e9
-        return {"kernels": names, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach / HBM_PEAK_GBS, 4), "avg_launch_ms": round(avg, 4),
-                "algorithmic_bytes_per_launch": by}
+        def roof(names, by):
+            ms = sum(prof[nm]["ms"] for nm in names if nm in prof)
+            la = max((prof[nm]["launches"] for nm in names if nm in prof), default=0)
+            if not la or ms <= 0:
+                return None
+            avg = ms / la
+            ach = by / (avg * 1e-3) / 1e9
+            return {"kernels": names, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(ach / HBM_PEAK_GBS, 4), "avg_launch_ms": round(avg, 4),
+                    "algorithmic_bytes_per_launch": by}
 
-    per = {"jaccard": roof(["jaccard"], b_j), "adamic_adar": roof(["adamic_adar"], b_aa),
-           "feature_cosine": roof(["featcos_normalise", "featcos_edges"], b_f)}
-    name = next((kk for kk in ("cg_reg", "cg_res") if kk in prof), None) or max(
-        prof, key=lambda kk: prof[kk]["ms"])
-    p = prof[name]
-    roofline = make_roofline(name, p["ms"] / p["launches"], p["bytes"] / p["launches"], p["launches"],
-                             "roman", world, steps=args.steps)
+        per = {"jaccard": roof(["jaccard"], b_j), "adamic_adar": roof(["adamic_adar"], b_aa),
+               "feature_cosine": roof(["featcos_normalise", "featcos_edges"], b_f)}
+        name = next((kk for kk in ("cg_reg", "cg_res") if kk in prof), None) or max(
+            prof, key=lambda kk: prof[kk]["ms"])
+        p = prof[name]
+        roofline = make_roofline(name, p["ms"] / p["launches"], p["bytes"] / p["launches"], p["launches"],
+                                 "roman", world, steps=args.steps)
+        extra = {"roofline": roofline, "scorer_rooflines": per,
+                 "kernels": {kk: {"launches": v["launches"], "ms": round(v["ms"], 3)}
+                             for kk, v in prof.items()}}
     result = {
         "metric": "scored edges/sec (Jaccard+AA+FeatCos+ApproxER)",
         "value": round(world * E * args.steps / elapsed, 1), "unit": "scored edges/s",
@@ -968,10 +1028,9 @@ def bench_scorers(args, world, rank, local_rank, dev, dist):
         "config": {"workload": "configs[1] Roman-empire all scorers", "n": n, "E": E, "features": f,
                    "jl_k": k, "cg_maxiter": 500, "blas_threads_order": args.blas_threads,
                    "parallelism": f"{world} replicas" if world > 1 else "1 GPU"},
-        "roofline": roofline, "scorer_rooflines": per,
-        "kernels": {kk: {"launches": v["launches"], "ms": round(v["ms"], 3)} for kk, v in prof.items()},
+        "roofline": None, **extra,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import gsparse_oracle as O
 
@@ -1057,6 +1116,14 @@ def main():
                     help="steps timed again in this box's default OpenBLAS order (secondary)")
     ap.add_argument("--cpu-sample-cols", type=int, default=64)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the result line's headline: the per-kernel times and roofline "
+                         "(HIP events in the timed steps), the box-order steps, the drop-in tie "
+                         "rule's cost and the CPU baseline (--box-order-steps and "
+                         "--no-cpu-baseline apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last step returned as "
+                         "DIR/<name>.npy (float32/float64; a fixed sample above 64 MB in all)")
     args = ap.parse_args()
 
     rehearse = os.environ.get("GSPARSE_REHEARSE") == "1"
@@ -1196,20 +1263,30 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    ctx.profile(True)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile(True)
+        ctx.profile_reset()
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    prof = ctx.profile_read()
-    ctx.profile(False)
+    prof = {}
+    if args.full:
+        prof = ctx.profile_read()
+        ctx.profile(False)
+    if args.dump_outputs and rank == 0:
+        if world > 1 and with_topk:  # this rank's own owner-pair scores, the whole mask
+            named = {"jaccard_own": last[0], "keep_mask": mask_out}
+        else:
+            named = {"jaccard": last[0], "approx_er": last[1] if with_er else None,
+                     "keep_mask": mask_out}
+        dump_outputs(args.dump_outputs, named)
     rank_ms = None
     if dist:
         # every rank's own time (the step time is the slowest rank's)
@@ -1266,11 +1343,12 @@ def main():
                             if with_topk else None),
                    "graph_gen_s": round(t_gen, 2)},
         "roofline": roofline,
-        "kernels": kernels,
     }
+    if args.full:
+        result["kernels"] = kernels
     if rank_ms is not None:
         result["rank_ms_per_step"] = rank_ms
-    if with_topk and world == 1 and sel_info.get("tied") is not None:
+    if args.full and with_topk and world == 1 and sel_info.get("tied") is not None:
         # secondary (not `value`): what the drop-in default tie_break="numpy" adds when the
         # cut is ambiguous -- the scores to the host and the reference's own np.argsort
         # (core.py:233-240) -- beside the device rule timed above
@@ -1290,7 +1368,7 @@ def main():
             "note": "secondary: GraphSparsifier.sparsify's default tie rule resolves an ambiguous "
                     "cut with the reference's np.argsort on the host; the line's value uses the "
                     "device rule (= np.argsort(kind='stable'))"}
-    if with_er and world == 1 and args.box_order_steps > 0:
+    if args.full and with_er and world == 1 and args.box_order_steps > 0:
         # secondary figure (not `value`): the same step in the OpenBLAS ddot order the
         # drop-in API reproduces by default on this box (threadpoolctl's thread count:
         # what the reference run here would use), beside the headline's fixed order
@@ -1313,7 +1391,7 @@ def main():
         result["box_blas_order"] = {"blas_threads": bt_box, "ms_per_step": round(ms_box, 2),
                                     "value": round(E / (ms_box * 1e-3), 1),
                                     "note": "secondary: the drop-in default order on this box"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # one BLAS thread: the fastest setting for this SciPy CG (n=22,662) on
         # the hosts measured (8 threads: 3.8x slower from ddot threading overhead)
         if args.workload == "roman":

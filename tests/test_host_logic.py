@@ -243,6 +243,38 @@ def test_counter_join_skips_first_call_kernels():
     assert bb["FETCH_SIZE_KB"] == 5.0 and bb["first_call_only"] == []
 
 
+def test_bench_dump_outputs_types_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: float arrays as they are, masks and counts as float32 / float64,
+    absent outputs left out, and an array above its share of the byte budget cut to the
+    same sorted sample in every run."""
+    import importlib.util
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.DUMP_BUDGET <= 64 * 1000 * 1000
+    monkeypatch.setattr(b, "DUMP_BUDGET", 4 * 1200)
+    big = np.arange(1000, dtype=np.float64) * 0.5
+    arrays = {"scores": torch.from_numpy(big), "mask": np.arange(5000) % 2 == 0,
+              "counts": np.arange(7, dtype=np.int64), "f32": np.ones(9, dtype=np.float32),
+              "absent": None}
+    b.dump_outputs(str(tmp_path / "a"), arrays)
+    b.dump_outputs(str(tmp_path / "b"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["counts", "f32", "mask", "scores"]
+    assert got["f32"].dtype == np.float32 and np.array_equal(got["f32"], arrays["f32"])
+    assert got["counts"].dtype == np.float64 and np.array_equal(got["counts"], np.arange(7))
+    share = 4 * 1200 // 4
+    assert got["scores"].dtype == np.float64 and got["scores"].size == share // 8
+    assert got["mask"].dtype == np.float32 and got["mask"].size == share // 4
+    assert np.all(np.diff(got["scores"]) > 0) and np.isin(got["scores"], big).all()
+    assert sum(a.nbytes for a in got.values()) <= 4 * 1200
+    for name, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy")), name
+
+
 def test_citation_like_rejects_impossible_counts():
     """more distinct citations than n (n - 1) / 2 pairs raise instead of
     looping; the limit itself is reachable."""

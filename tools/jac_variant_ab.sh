@@ -14,7 +14,7 @@ tail -1 "$O/pytest.log"
 for rep in 1 2; do
   for v in main "$@"; do
     if [ "$v" = main ]; then lib=$PKG/libgsparse.so; else lib=$PKG/libgsparse_$v.so; fi
-    GSPARSE_LIB=$lib timeout -k 10 300 python bench.py --workload rmat --steps 10 --warmup 2 --no-cpu-baseline > "$O/bench_${v}_$rep.json" 2> "$O/bench_${v}_$rep.err" || { tail -5 "$O/bench_${v}_$rep.err"; exit 1; }
+    GSPARSE_LIB=$lib timeout -k 10 300 python bench.py --full --workload rmat --steps 10 --warmup 2 --no-cpu-baseline > "$O/bench_${v}_$rep.json" 2> "$O/bench_${v}_$rep.err" || { tail -5 "$O/bench_${v}_$rep.err"; exit 1; }
     python3 -c "import json;a=json.load(open('$O/bench_${v}_$rep.json'));print('$v', a['ms_per_step'], a['roofline']['avg_launch_ms'])"
   done
 done

@@ -13,6 +13,6 @@ for q in 1 0; do
   echo "QR=$q"; grep -v "^\s*$" "$O/probe_q$q.txt" | tail -3
 done
 for q in 1 0; do
-  GSPARSE_REG_QR=$q timeout -k 10 200 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$O/bench_q$q.json" 2> "$O/bench_q$q.err" || { tail -20 "$O/bench_q$q.err"; exit 1; }
+  GSPARSE_REG_QR=$q timeout -k 10 200 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$O/bench_q$q.json" 2> "$O/bench_q$q.err" || { tail -20 "$O/bench_q$q.err"; exit 1; }
   python3 -c "import json;a=json.load(open('$O/bench_q$q.json'));print('QR=$q ms/step',a['ms_per_step'],'kernel ms',a['roofline']['avg_launch_ms'])"
 done

@@ -10,6 +10,6 @@ timeout -k 10 500 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -q --ti
 tail -1 "$O/pytest.log"
 for sp in auto 0; do
   if [ $sp = auto ]; then unset GSPARSE_REG_SPLIT; else export GSPARSE_REG_SPLIT=$sp; fi
-  timeout -k 10 200 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$O/bench_$sp.json" 2> "$O/bench_$sp.err" || { tail -20 "$O/bench_$sp.err"; exit 1; }
+  timeout -k 10 200 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$O/bench_$sp.json" 2> "$O/bench_$sp.err" || { tail -20 "$O/bench_$sp.err"; exit 1; }
   python3 -c "import json;a=json.load(open('$O/bench_$sp.json'));print('split=$sp ms/step',a['ms_per_step'],'kernel ms',a['roofline']['avg_launch_ms'])"
 done

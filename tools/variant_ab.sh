@@ -16,6 +16,6 @@ for v in "$@"; do
   echo "$v: $(tail -1 $O/pytest_$v.log)"
   GSPARSE_LIB=$lib GSPARSE_RES_PROF=1 timeout -k 10 200 python tools/cg_probe.py 22662 256 > "$O/probe_$v.txt" 2>&1 || { tail -20 "$O/probe_$v.txt"; exit 1; }
   grep -v "^\s*$" "$O/probe_$v.txt" | tail -2
-  GSPARSE_LIB=$lib timeout -k 10 200 python bench.py --steps 5 --warmup 1 --no-cpu-baseline > "$O/bench_$v.json" 2> "$O/bench_$v.err" || { tail -20 "$O/bench_$v.err"; exit 1; }
+  GSPARSE_LIB=$lib timeout -k 10 200 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > "$O/bench_$v.json" 2> "$O/bench_$v.err" || { tail -20 "$O/bench_$v.err"; exit 1; }
   python3 -c "import json;a=json.load(open('$O/bench_$v.json'));print('$v ms/step',a['ms_per_step'],'kernel ms',a['roofline']['avg_launch_ms'])"
 done
