@@ -6,15 +6,9 @@
 // indices; keep_lowest: the lowest), with a device exclusive scan over the
 // tie flags.  NaN orders last (np.sort), -0.0 == +0.0.
 #include "gs_internal.hpp"
+#include "gs_keys.hpp"
 
 namespace gs {
-
-__device__ __forceinline__ uint64_t order_key(double x) {
-    if (x != x) return ~0ull;
-    if (x == 0.0) x = 0.0;  // -0.0 -> +0.0
-    uint64_t b = (uint64_t)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 static double key_to_double(uint64_t k) {
     uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;

@@ -258,7 +258,9 @@ class GraphSparsifier:
         columns are chosen by the same ``np.argsort`` over its incident scores,
         and the fill takes the first non-guaranteed entries of
         ``np.argsort(scores)[::-1]`` -- both on the device, with the reference's
-        own calls only where its argsort order decides."""
+        own calls only where its argsort order decides.
+        ``last_selection`` records the path: ``phase1`` ("device", or "host" for
+        ``min_edges_per_node < 1`` or NaN scores) and ``n_ambiguous``."""
         if not 0 < retention_ratio <= 1:
             raise ValueError(f"retention_ratio must be in (0, 1], got {retention_ratio}")
         if retention_ratio == 1.0:
@@ -266,9 +268,10 @@ class GraphSparsifier:
                 return self.data.clone(), torch.ones(self.num_edges, dtype=torch.bool)
             return self.data.clone()
         scores = self.compute_scores(metric)
+        self.last_selection = {}
         mask = degree_aware_mask_device(self._engine, scores, self.data.edge_index.cpu().numpy(),
                                         self.num_nodes, self.num_edges, retention_ratio,
-                                        min_edges_per_node)
+                                        min_edges_per_node, info=self.last_selection)
         sparse_edge_index = self.data.edge_index[:, torch.from_numpy(mask).to(
             self.data.edge_index.device)].to(self.device)
         sparse_data = self.data.clone()

@@ -409,6 +409,33 @@ class Engine:
                       GS_HOST, int(src.shape[0]), int(num_nodes), ptr(pick), GS_HOST)
         return pick[:num_nodes]
 
+    SEGK_CLASSES = ("empty", "all", "short", "lds", "stream")
+
+    def segment_topk(self, scores: np.ndarray, src: np.ndarray, num_nodes: int, k: int):
+        """gs_segment_topk: per node the set of its min(k, d) top-scoring columns.
+
+        Returns ``(mask, status, info)``: ``mask`` bool[E], True on the guaranteed
+        columns of the decided nodes; ``status`` uint8[n], 0 (no column), 1
+        (decided) or 2 (np.argsort's order decides: no byte of that node is set);
+        ``info`` = ``n_guaranteed``, ``n_ambiguous`` and ``classes`` (nodes handled
+        per kernel class, keyed by SEGK_CLASSES)."""
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        src = np.ascontiguousarray(src, dtype=np.int64)
+        E = int(src.shape[0])
+        if E > scores.shape[0]:  # NumPy's error for scores[column], as the reference raises it
+            raise IndexError(f"index {E - 1} is out of bounds for axis 0 with size "
+                             f"{scores.shape[0]}")
+        mask = np.zeros(max(E, 1), dtype=np.uint8)
+        status = np.zeros(max(num_nodes, 1), dtype=np.uint8)
+        counts = np.zeros(len(self.SEGK_CLASSES), dtype=np.int64)
+        ng, na = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.ctx.call("gs_segment_topk", ptr(scores), GS_HOST, int(scores.shape[0]), ptr(src),
+                      GS_HOST, E, int(num_nodes), int(k), ptr(mask), GS_HOST, ptr(status), GS_HOST,
+                      ctypes.byref(ng), ctypes.byref(na), ptr(counts), len(counts))
+        info = {"n_guaranteed": ng.value, "n_ambiguous": na.value,
+                "classes": dict(zip(self.SEGK_CLASSES, (int(v) for v in counts)))}
+        return mask[:E].view(bool), status[:num_nodes], info
+
     def topk_mask(self, scores, num_edges: int, num_keep: int, keep_lowest: bool, out=None):
         """Device mask + (cut, #beyond, #tied) -- see gs_topk_mask.  ``scores``: a
         numpy array or a CUDA float64 tensor; ``out``: an optional CUDA uint8/bool

@@ -73,30 +73,47 @@ def degree_aware_mask(scores: np.ndarray, edge_index: np.ndarray, num_nodes: int
 
 def degree_aware_mask_device(engine, scores: np.ndarray, edge_index: np.ndarray,
                              num_nodes: int, num_edges: int, retention_ratio: float,
-                             min_edges_per_node: int = 1) -> np.ndarray:
+                             min_edges_per_node: int = 1, info: dict | None = None) -> np.ndarray:
     """degree_aware_mask with both phases on the MI355X; the same result.
 
-    Phase 1: gs_segment_argmax gives every node's unique top column; nodes
-    where np.argsort's order decides (ties at the maximum, NaN) take the
+    Phase 1: gs_segment_argmax (min_edges_per_node == 1) gives every node's unique
+    top column, gs_segment_topk (>= 2) the unique set of its k best columns; nodes
+    where np.argsort's order decides (ties at the node's cut, NaN) take the
     reference's own call.  Phase 2: a device radix select over the scores with
     the guaranteed columns removed; an ambiguous tie block at the cut (or any
-    NaN) takes the reference's own descending argsort walk."""
+    NaN) takes the reference's own descending argsort walk.
+
+    ``info`` (optional dict) receives which path ran: ``phase1`` ("device" or
+    "host"), ``n_ambiguous`` (nodes resolved by the reference's call) and, for the
+    segmented top-k, its ``classes`` counts."""
+    if info is None:
+        info = {}
     scores = np.asarray(scores, dtype=np.float64)
     src = np.ascontiguousarray(np.asarray(edge_index)[0], dtype=np.int64)
-    if min_edges_per_node != 1 or num_edges > len(scores) or np.isnan(scores).any():
+    if (not isinstance(min_edges_per_node, (int, np.integer)) or min_edges_per_node < 1
+            or num_edges > len(scores) or np.isnan(scores).any()):
+        info.update(phase1="host", n_ambiguous=0)
         return degree_aware_mask(scores, edge_index, num_nodes, num_edges, retention_ratio,
                                  min_edges_per_node)
     num_keep = int(num_edges * retention_ratio)
-    pick = engine.segment_argmax(scores, src[:num_edges], num_nodes)
-    mask = np.zeros(num_edges, dtype=bool)
-    mask[pick[pick >= 0]] = True
-    amb = np.nonzero(pick == -2)[0]
+    k = int(min_edges_per_node)
+    if k == 1:
+        pick = engine.segment_argmax(scores, src[:num_edges], num_nodes)
+        mask = np.zeros(num_edges, dtype=bool)
+        mask[pick[pick >= 0]] = True
+        amb = np.nonzero(pick == -2)[0]
+    else:
+        mask, status, seg = engine.segment_topk(scores, src[:num_edges], num_nodes, k)
+        mask = mask.copy()
+        amb = np.nonzero(status == 2)[0]
+        info["classes"] = seg["classes"]
+    info.update(phase1="device", n_ambiguous=int(len(amb)))
     if len(amb):
         order = np.argsort(src, kind="stable")
         bounds = np.searchsorted(src[order], np.arange(num_nodes + 1))
         for node in amb:
             incident = order[bounds[node]:bounds[node + 1]]
-            mask[incident[np.argsort(scores[incident])[-1:]]] = True
+            mask[incident[np.argsort(scores[incident])[-k:]]] = True
     have = int(mask.sum())
     if have >= num_keep:
         return mask

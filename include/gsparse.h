@@ -229,8 +229,8 @@ int gs_topk_mask(gs_ctx *ctx, const double *scores, int s_loc, int64_t nnz, int6
  * edge_weights[idx] for every column, metric_backbone.py:73-74, and raises
  * IndexError).  n_relax (optional) returns the number of edge relaxations
  * performed. */
-/* sparsify_degree_aware phase 1 (core.py:415-428, min_edges_per_node = 1):
- * for every node u, pick[u] = the edge_index column i (src[i] == u) holding
+/* sparsify_degree_aware phase 1 (core.py:415-428) for min_edges_per_node = 1
+ * (any other budget: gs_segment_topk below): for every node u, pick[u] = the edge_index column i (src[i] == u) holding
  * the unique maximum of scores[i], -1 if u has no column, -2 when the
  * reference's np.argsort order decides (ties at the maximum or a NaN).
  * scores are indexed by column as the reference indexes them (needs E <=
@@ -238,6 +238,32 @@ int gs_topk_mask(gs_ctx *ctx, const double *scores, int s_loc, int64_t nnz, int6
 int gs_segment_argmax(gs_ctx *ctx, const double *scores, int s_loc, int64_t nscores,
                       const int64_t *src, int src_loc, int64_t E, int64_t n, int64_t *pick,
                       int pick_loc);
+
+/* sparsify_degree_aware phase 1 for any min_edges_per_node = k >= 1
+ * (core.py:415-428): a segmented top-k.  For every node u with d columns
+ * (src[i] == u), the set of its min(k, d) highest-scoring columns, on the
+ * keys of gs_topk_mask (-0.0 == +0.0, NaN the largest key):
+ *   d <= k: all its columns, status 1 (never ambiguous);
+ *   d >  k: t = the k-th largest key, gt = keys above t, eq = keys equal to t;
+ *           gt + eq == k: the columns with key >= t, status 1; otherwise, or
+ *           with a NaN in the segment, the reference's np.argsort order decides
+ *           inside the tie block: status 2 and none of u's mask bytes is set
+ *           (the caller makes the reference's own call for u);
+ *   d == 0: status 0.
+ * mask[E]: 1 = guaranteed column of a decided node.  n_guaranteed = mask bytes
+ * set, n_ambiguous = nodes of status 2.  class_counts[0..ncounts): nodes handled
+ * per GS_SEGK_* class (by segment length: SHORT one key per lane of a sub-wave
+ * group, LDS one workgroup with the keys staged in LDS, STREAM one workgroup
+ * re-reading its keys per radix digit; GSPARSE_SEGK_SHORT_MAX / _LDS_MAX lower
+ * the class limits).  A src sorted ascending needs no grouping pass.  Errors as
+ * gs_segment_argmax (E > nscores, src out of [0, n): GS_EINVAL); k < 1 is
+ * GS_EINVAL. */
+enum { GS_SEGK_EMPTY = 0, GS_SEGK_ALL, GS_SEGK_SHORT, GS_SEGK_LDS, GS_SEGK_STREAM, GS_SEGK_CLASSES };
+int gs_segment_topk(gs_ctx *ctx, const double *scores, int s_loc, int64_t nscores,
+                    const int64_t *src, int src_loc, int64_t E, int64_t n, int64_t k,
+                    uint8_t *mask, int mask_loc, uint8_t *status, int status_loc,
+                    int64_t *n_guaranteed, int64_t *n_ambiguous, int64_t *class_counts,
+                    int ncounts);
 
 int gs_metric_backbone(gs_ctx *ctx, int64_t n, int64_t E, const int64_t *src,
                        const int64_t *dst, const double *w, int64_t nw, int loc, double eps,
