@@ -1,6 +1,7 @@
 // gs_cg_reg.hip -- host side of the register-resident CG (ApproxER mode 5): the
 // ELL-8 copy of L_reg with p codes, the LDS plan, geometry and launch.  The kernel
 // and its design notes are in gs_cg_reg.hpp.
+#include "gs_cg.hpp"
 #include "gs_cg_reg.hpp"
 
 #ifndef GS_CG_XG
@@ -99,12 +100,12 @@ static int reg_geometry(int NT, int T, const int64_t *len, int &G) {
 
 // workgroup size and slots: 512 threads (two waves per SIMD, k_cg_regwide) where the
 // slots fit 44, else 256 threads (one wave per SIMD, 512 registers per lane,
-// k_cg_regres) with up to 88.  GSPARSE_REG_NT=256 forces the one-wave form.
-static bool reg_pick(int64_t n, int T, const int64_t *len, int &NT, int &G, int &R) {
+// k_cg_regres) with up to 88.  reg_nt = 256 (the plan's, GSPARSE_REG_NT) forces the
+// one-wave form.
+static bool reg_pick(int64_t n, int T, const int64_t *len, int reg_nt, int &NT, int &G, int &R) {
     if (n <= 0 || n >= 0x8000) return false;
     int g = 0;
-    const char *e = getenv("GSPARSE_REG_NT");
-    const bool narrow_only = e && atoi(e) == 256;
+    const bool narrow_only = reg_nt == 256;
     int r = narrow_only ? -1 : reg_geometry(512, T, len, g);
     if (r >= 0 && r <= 44) {
         NT = 512, G = g;
@@ -118,24 +119,28 @@ static bool reg_pick(int64_t n, int T, const int64_t *len, int &NT, int &G, int 
     return true;
 }
 
-bool cg_regres_applies(int64_t n, int T, const int64_t *len) {
+bool cg_regres_applies(int64_t n, int T, const int64_t *len, int reg_nt) {
     int NT, G, R;
-    return reg_pick(n, T, len, NT, G, R);
+    return reg_pick(n, T, len, reg_nt, NT, G, R);
 }
 
-bool cg_regres_wide(int64_t n, int T, const int64_t *len) {
+bool cg_regres_wide(int64_t n, int T, const int64_t *len, int reg_nt) {
     int NT = 0, G, R;
-    return reg_pick(n, T, len, NT, G, R) && NT == 512;
+    return reg_pick(n, T, len, reg_nt, NT, G, R) && NT == 512;
 }
 
-void cg_regres_solve(gs_ctx *c, int64_t n, const int64_t *lp, const int32_t *li, const double *lv,
-                     int unit, int dcount, const double *diag, const double *Rr, int64_t ld,
-                     int64_t col0, int64_t ncols, int32_t maxiter, double rtol, int T,
-                     const int64_t *ha, const int64_t *hlen, double *Xc, int64_t ldn,
-                     int32_t *iters, int64_t slots, long long *prof) {
+// columns [col0, col0 + ncols) of L_reg (CSR lp/li/lv, n > 0 rows) into Xc (column-major,
+// ldn per column), the iterations each ran into iters
+static void regres_run(gs_ctx *c, const CgPlan &plan, int64_t n, const int64_t *lp, const int32_t *li,
+                       const double *lv, int unit, int dcount, const double *diag, const double *Rr,
+                       int64_t ld, int64_t col0, int64_t ncols, int32_t maxiter, double rtol,
+                       double *Xc, int64_t ldn, int32_t *iters, long long *prof) {
     hipStream_t s = c->stream;
+    const int T = plan.ch.count;
+    const int64_t *ha = plan.ch.a, *hlen = plan.ch.len;
+    const int64_t slots = plan.slots;
     int NT = 0, G = 0, rsel = 0;
-    GS_CHECK(reg_pick(n, T, hlen, NT, G, rsel), GS_EUNSUPPORTED,
+    GS_CHECK(reg_pick(n, T, hlen, plan.reg_nt, NT, G, rsel), GS_EUNSUPPORTED,
              "register-resident CG: n=%lld, %d chunks out of range", (long long)n, T);
     // LDS: p (each chunk's LDS-resident prefix, in chunk order), the zero and scratch
     // slots, (one-wave form) 2 diagonal slots per thread, 6 x 32 T doubles of chain
@@ -170,8 +175,7 @@ void cg_regres_solve(gs_ctx *c, int64_t n, const int64_t *lp, const int32_t *li,
             left -= align;
         }
     }
-    if (const char *e = getenv("GSPARSE_REG_KEEP"))
-        for (int t = 0; t < T; ++t) keep[t] = std::min<int64_t>(keep[t], atoll(e));
+    for (int t = 0; t < T; ++t) keep[t] = std::min<int64_t>(keep[t], plan.reg_keep);
     int64_t zs = 0;
     for (int t = 0; t < T; ++t) {
         lbase[t] = zs;
@@ -249,12 +253,11 @@ void cg_regres_solve(gs_ctx *c, int64_t n, const int64_t *lp, const int32_t *li,
     split_abort_poll(c, false);
     if (c->reg_split_off && c->reg_split_off_epoch != c->g.epoch) c->reg_split_off = false;  // new graph
     if (NT == 512 && T >= 2 && ncols > 0 && !c->reg_split_off) {
-        const char *se = getenv("GSPARSE_REG_SPLIT");
-        const int forced = se ? atoi(se) : -1;
+        const int forced = plan.reg_split;
         if (forced >= 2) {
             P = std::min(forced, T);
             W = 0;
-        } else if (forced < 0 && !getenv("GSPARSE_CG_SLOTS") && getenv("GSPARSE_REG_SPLIT_AUTO")) {
+        } else if (forced < 0 && !plan.slots_forced && plan.reg_split_auto) {
             // (round 6: off by default.  With one SpMV per iteration a whole column-iteration
             // takes ~31 us, and the last round solved whole inside the same launch -- each CU
             // starts its tail column as soon as its own columns are done -- matches or beats
@@ -425,7 +428,7 @@ void cg_regres_solve(gs_ctx *c, int64_t n, const int64_t *lp, const int32_t *li,
     int wclk_khz = 100000;
     GS_HIP(hipDeviceGetAttribute(&wclk_khz, hipDeviceAttributeWallClockRate, c->device));
     B.spinmax = 20 * std::max(wclk_khz, 1);
-    if (const char *e = getenv("GSPARSE_REG_SPLIT_SPIN")) B.spinmax = atoi(e);
+    if (plan.reg_split_spin != INT32_MIN) B.spinmax = plan.reg_split_spin;
     const unsigned grid = (unsigned)(groups * P);
     launch_whole();
     if (Gs == 4) regwide_split_launch_g4(B, Rs, ufast, dyns, grid, s);
@@ -461,6 +464,21 @@ void cg_regres_solve(gs_ctx *c, int64_t n, const int64_t *lp, const int32_t *li,
     GS_HIP(hipEventRecord(c->split_abort_ev, s));
     c->split_abort_pending = true;
     c->split_abort_parts = P;
+}
+
+void cg_regres_solve(gs_ctx *c, const CgPlan &plan, int64_t col0, int64_t col1, int32_t maxiter,
+                     double rtol) {
+    ErState &er = c->er;
+    const int64_t ncols = col1 - col0;
+    int32_t *iters = col_ptrs(er).iters;
+    const ResCommon rc = res_begin(c, plan, ncols);
+    GS_HIP(hipMemsetAsync(iters + col0, 0, sizeof(int32_t) * ncols, c->stream));
+    hipEvent_t t0 = prof_begin(c);
+    if (er.n)
+        regres_run(c, plan, er.n, er.lp.as<int64_t>(), er.li.as<int32_t>(), er.lv.as<double>(),
+                   rc.unit, rc.dcount, rc.sdiag, er.Rr.as<double>(), er.ld, col0, ncols, maxiter, rtol,
+                   rc.Xc, rc.ldn, iters, rc.prof);
+    res_end(c, rc, t0, "cg_reg", col0, ncols);
 }
 
 // The abort word of the last split launch, once its copy has landed (never waits unless

@@ -6,7 +6,7 @@
 // maxiter 500, rtol 1e-6) whose dot products follow OpenBLAS-SkylakeX ddot's
 // order for T threads: T contiguous chunks, in each 32 FMA accumulator
 // chains (chain j: rows a_t + j, a_t + j + 32, ...), then a fixed fold, a
-// 16-row block and an FMA tail (gs_er.hip chunk_dot).
+// 16-row block and an FMA tail (gs_cg.hpp chunk_dot).
 //
 // Mode 4 (k_cg_resident) keeps a column's r, p, q, x in Infinity-Cache-
 // resident slots and streams ~2 MB through each CU per column-iteration; its

@@ -70,6 +70,16 @@ def er_split(k: int, parts: int) -> list[int]:
     return b.tolist()
 
 
+def er_plan(n: int, lnnz: int, ncols: int, blas_threads: int) -> dict:
+    """The plan gs_er_solve follows for ncols columns of an n-row system whose L_reg
+    has lnnz entries, under the GSPARSE_CG_* / _RES_* / _REG_* variables as they are
+    now (gs_er_plan; host code, no device): solver mode, columns per lane, chain rows
+    per trip, BLAS chunks."""
+    o = np.zeros(4, dtype=np.int32)
+    _lib.check(_lib.lib().gs_er_plan(n, lnnz, ncols, blas_threads, ptr(o)), "gs_er_plan")
+    return dict(zip(("mode", "cpl", "ru", "chunks"), o.tolist()))
+
+
 class Engine:
     """Scorers over the graph resident in ``ctx``."""
 

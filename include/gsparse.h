@@ -209,6 +209,11 @@ int gs_er_copy_z(gs_ctx *ctx, int64_t col0, int64_t col1, double *out, int loc);
 /* Column blocks of the pairwise tree of k at depth log2(parts): bounds has
  * parts+1 entries.  parts must be a power of two. */
 int gs_er_split(int64_t k, int32_t parts, int64_t *bounds);
+/* The plan gs_er_solve follows for ncols columns of an n-row system whose L_reg has
+ * lnnz entries, with blas_threads ddot threads and the GSPARSE_CG_* / GSPARSE_RES_* /
+ * GSPARSE_REG_* variables as they are now: out = {solver mode 0..5, columns per lane,
+ * chain rows per trip, BLAS chunks}.  Host code only: needs no context and no device. */
+int gs_er_plan(int64_t n, int64_t lnnz, int64_t ncols, int32_t blas_threads, int32_t out[4]);
 
 /* ---- selection: GraphSparsifier.sparsify core.py:229-242 -----------------
  * mask[E] (uint8): the num_keep highest (keep_lowest: lowest) of the nnz

@@ -9,6 +9,8 @@ identical keep masks for top-k (numpy tie mode), the metric backbone, the
 sampled and degree-aware selections.
 """
 
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -214,6 +216,35 @@ def test_split_tail_in_offset_column_blocks(gs, chunked_er, monkeypatch):
     assert bits_equal(e.er_scores(0, k, finalize=False), whole)
     # the blocks' partial sums are pairwise-tree halves of the whole sum
     assert bits_equal(0.0 + (sums[0] + sums[1]), whole)
+
+
+@pytest.mark.parametrize("threads", [8, 3])
+def test_default_plan_is_the_solver_that_runs(gs, chunked_er, threads, monkeypatch):
+    """No solver variable set: the profile holds the entry of the mode gs_er_plan gives
+    for this solve and of no other mode, and the scores are the oracle's bits."""
+    for name in list(os.environ):
+        if name.startswith(("GSPARSE_CG_", "GSPARSE_RES_", "GSPARSE_REG_")):
+            monkeypatch.delenv(name)
+    n, graphs_ = chunked_er
+    ei, ref = graphs_["unit"]
+    ip, ix, d = O.canonical_csr(ei, n)
+    # L_reg = diag(rowsum A) + 1e-6 I - A: a diagonal entry per row, and A's off-diagonal ones
+    rows = np.repeat(np.arange(n), np.diff(ip))
+    lnnz = n + int(np.count_nonzero((rows != ix) & (d != 0)))
+    plan = gs.engine.er_plan(n, lnnz, gs.engine.jl_dim(n, 0.9), threads)
+    entry = {5: "cg_reg", 4: "cg_res", 3: "cg_spmv", 2: "cg_q", 1: "cg_pq", 0: "cg_pq"}
+    sp_ = gs.GraphSparsifier(gs.Data(edge_index=torch.from_numpy(ei), num_nodes=n), "cpu")
+    ctx = sp_._engine.ctx
+    ctx.profile(True)
+    ctx.profile_reset()
+    er = sp_._engine.approx_er(epsilon=0.9, max_cg_iters=60, blas_threads=threads)
+    prof = ctx.profile_read()
+    ctx.profile(False)
+    print("plan", plan, "profile", sorted(prof))
+    want = entry[plan["mode"]]
+    assert prof.get(want, {}).get("launches", 0) > 0, (plan, sorted(prof))
+    assert not (set(entry.values()) - {want}) & set(prof), (plan, sorted(prof))
+    assert bits_equal(er, ref[threads])
 
 
 def test_approx_er_roman_full_bit_exact(gs):
