@@ -15,7 +15,7 @@
 namespace gs {
 
 template <class T, class F>
-__device__ __forceinline__ T pw_leaf(int64_t off, int64_t n, F &get) {
+__host__ __device__ __forceinline__ T pw_leaf(int64_t off, int64_t n, F &get) {
     if (n < 8) {
         T r = T(0);
         for (int64_t i = 0; i < n; ++i) r = r + get(off + i);
@@ -58,6 +58,52 @@ __device__ T pw_sum(int64_t n, F get) {
         if (st_s[sp] == 0) {
             if (nn <= 128) {
                 ret = pw_leaf<T>(off, nn, get);
+            } else {
+                st_s[sp] = 1;
+                ++sp;
+                off_s[sp] = off;
+                n_s[sp] = n2;
+                st_s[sp] = 0;
+                continue;
+            }
+        } else if (st_s[sp] == 1) {
+            left_s[sp] = ret;
+            st_s[sp] = 2;
+            ++sp;
+            off_s[sp] = off + n2;
+            n_s[sp] = nn - n2;
+            st_s[sp] = 0;
+            continue;
+        } else {
+            ret = left_s[sp] + ret;
+        }
+        if (sp == 0) return ret;
+        --sp;
+    }
+}
+
+// The same walk over the nodes above a cut: a node of at most `cut` (>= 128) terms is
+// handed to leaf(off, n) whole, the others split as above and add left + right.  With
+// leaf = "the pairwise sum of that range" the result is pw_sum's without the leading
+// identity; the leaves are visited in ascending offset, so a caller may also just
+// collect them (the tree's shape depends on n alone).
+template <class T, class L>
+__host__ __device__ T pw_tree(int64_t n, int64_t cut, L leaf) {
+    int64_t off_s[48], n_s[48];
+    T left_s[48];
+    unsigned char st_s[48];
+    int sp = 0;
+    off_s[0] = 0;
+    n_s[0] = n;
+    st_s[0] = 0;
+    T ret = T(0);
+    for (;;) {
+        int64_t off = off_s[sp], nn = n_s[sp];
+        int64_t n2 = nn / 2;
+        n2 -= n2 % 8;
+        if (st_s[sp] == 0) {
+            if (nn <= cut) {
+                ret = leaf(off, nn);
             } else {
                 st_s[sp] = 1;
                 ++sp;

@@ -29,7 +29,7 @@ from ._lib import Context
 from .data import Data
 from .engine import Engine
 from .metric_backbone import compute_metric_backbone
-from .selection import degree_aware_mask_device, numpy_topk_mask, sampled_mask
+from .selection import degree_aware_mask_device, numpy_topk_mask, sampled_mask_device
 
 
 def _device_index(device) -> int | None:
@@ -232,8 +232,11 @@ class GraphSparsifier:
                          return_mask: bool = False):
         """Score-proportional sampling without replacement (core.py:281-357).
 
-        NumPy's ``Generator.choice`` stream defines the result; it runs on the
-        host exactly as in the reference."""
+        NumPy's ``Generator.choice`` stream defines the result: its rejection rounds
+        run on the device (gs_sample_mask) and give the same mask bit for bit, with
+        the reference's own call only for degenerate scores, where NumPy raises
+        (SURVEY §8(f) rank 1).  ``last_selection`` records the path: ``path``
+        ("device" or "host"), ``rounds`` and ``draws``."""
         if not 0 < retention_ratio <= 1:
             raise ValueError(f"retention_ratio must be in (0, 1], got {retention_ratio}")
         if retention_ratio == 1.0:
@@ -241,7 +244,9 @@ class GraphSparsifier:
                 return self.data.clone(), torch.ones(self.num_edges, dtype=torch.bool)
             return self.data.clone()
         scores = self.compute_scores(metric)
-        mask = sampled_mask(scores, self.num_edges, retention_ratio, seed)
+        self.last_selection = {}
+        mask = sampled_mask_device(self._engine, scores, self.num_edges, retention_ratio, seed,
+                                   info=self.last_selection)
         sparse_edge_index = self.data.edge_index[:, torch.from_numpy(mask).to(
             self.data.edge_index.device)].to(self.device)
         sparse_data = self.data.clone()

@@ -319,15 +319,7 @@ class Engine:
         """The same R drawn on the device (PCG64 + NumPy's ziggurat); cols = (c0, c1):
         every normal is parsed, only R[:, c0:c1] is stored and projected."""
         c0, c1 = cols if cols is not None else (0, k)
-        st = rng.bit_generator.state
-        if st.get("bit_generator") != "PCG64":
-            raise NotImplementedError("device ziggurat supports the PCG64 bit generator")
-        s, inc = int(st["state"]["state"]), int(st["state"]["inc"])
-        m64 = (1 << 64) - 1
-        if st.get("has_uint32"):
-            raise NotImplementedError("PCG64 state with a buffered uint32")
-        self.ctx.call("gs_er_project_pcg64_cols", s >> 64, s & m64, inc >> 64, inc & m64,
-                      float(np.sqrt(k)), c0, c1)
+        self.ctx.call("gs_er_project_pcg64_cols", *self._pcg64_words(rng), float(np.sqrt(k)), c0, c1)
 
     def er_solve(self, col0: int, col1: int, maxiter: int, rtol: float, blas_threads: int):
         self.ctx.call("gs_er_solve", col0, col1, maxiter, rtol, blas_threads)
@@ -445,6 +437,65 @@ class Engine:
         info = {"n_guaranteed": ng.value, "n_ambiguous": na.value,
                 "classes": dict(zip(self.SEGK_CLASSES, (int(v) for v in counts)))}
         return mask[:E].view(bool), status[:num_nodes], info
+
+    # -- score-proportional sampling (gs_sample_*, include/gsparse.h) ----------
+    # GS_SAMPLE_TILE / GS_SAMPLE_SUBTREE: the sizes at which the ordered cumsum starts
+    # a new LDS tile and the pairwise total a new subtree
+    SAMPLE_TILE, SAMPLE_SUBTREE = 1024, 2048
+
+    @staticmethod
+    def _pcg64_words(rng: np.random.Generator):
+        """(state_hi, state_lo, inc_hi, inc_lo) of a Generator(PCG64)."""
+        st = rng.bit_generator.state
+        if st.get("bit_generator") != "PCG64":
+            raise NotImplementedError("the device stream supports the PCG64 bit generator")
+        if st.get("has_uint32"):
+            raise NotImplementedError("PCG64 state with a buffered uint32")
+        s, inc = int(st["state"]["state"]), int(st["state"]["inc"])
+        m64 = (1 << 64) - 1
+        return s >> 64, s & m64, inc >> 64, inc & m64
+
+    def sample_mask(self, scores: np.ndarray, num_edges: int, num_keep: int,
+                    rng: np.random.Generator):
+        """gs_sample_mask: the set ``rng.choice(num_edges, num_keep, replace=False, p=probs)``
+        draws from ``rng``'s current state (the generator itself is not advanced).
+
+        Returns ``(mask, status, rounds, draws)``: ``status`` 0 = ``mask`` (bool[E]) was
+        written by the device rounds, 1 = degenerate input, NumPy's own call decides
+        (``mask`` is None)."""
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        words = self._pcg64_words(rng)
+        mask = np.zeros(max(int(num_edges), 1), dtype=np.uint8)
+        status, rounds, draws = ctypes.c_int32(1), ctypes.c_int64(0), ctypes.c_int64(0)
+        self.ctx.call("gs_sample_mask", ptr(scores), GS_HOST, int(scores.shape[0]), int(num_edges),
+                      int(num_keep), *words, ptr(mask), GS_HOST, ctypes.byref(status),
+                      ctypes.byref(rounds), ctypes.byref(draws))
+        if status.value != 0:
+            return None, status.value, 0, 0
+        return mask[:num_edges].view(bool), 0, rounds.value, draws.value
+
+    def pcg64_doubles(self, rng: np.random.Generator, offset: int, n: int) -> np.ndarray:
+        """gs_pcg64_doubles: ``rng.random(offset + n)[offset:]`` drawn on the device."""
+        out = np.empty(max(n, 1), dtype=np.float64)
+        self.ctx.call("gs_pcg64_doubles", *self._pcg64_words(rng), int(offset), int(n), ptr(out),
+                      GS_HOST)
+        return out[:n]
+
+    def sample_probs(self, scores: np.ndarray):
+        """gs_sample_probs: (probs, total) of sparsify_sampled's normalisation."""
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        p = np.empty(scores.shape[0], dtype=np.float64)
+        total = ctypes.c_double(0.0)
+        self.ctx.call("gs_sample_probs", ptr(scores), GS_HOST, int(scores.shape[0]), ptr(p), GS_HOST,
+                      ctypes.byref(total))
+        return p, total.value
+
+    def cumsum_ordered(self, p: np.ndarray) -> np.ndarray:
+        """gs_cumsum_ordered: ``np.cumsum(p)`` (the sequential fp64 add chain)."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        out = np.empty(max(p.shape[0], 1), dtype=np.float64)
+        self.ctx.call("gs_cumsum_ordered", ptr(p), GS_HOST, int(p.shape[0]), ptr(out), GS_HOST)
+        return out[:p.shape[0]]
 
     def topk_mask(self, scores, num_edges: int, num_keep: int, keep_lowest: bool, out=None):
         """Device mask + (cut, #beyond, #tied) -- see gs_topk_mask.  ``scores``: a

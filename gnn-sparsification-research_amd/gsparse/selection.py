@@ -2,9 +2,11 @@
 
 ``sparsify_sampled`` (core.py:333-350) is a draw from NumPy's
 ``Generator.choice`` stream and ``sparsify_degree_aware`` (core.py:415-453)
-orders ties with ``np.argsort``; both are O(E) consumers of the device
-scores kept on the host verbatim (SURVEY §8(f) rank 1 is their device port).
-The functions take plain arrays so they are testable without a GPU.
+orders ties with ``np.argsort``.  The plain functions make the reference's
+own calls on the host; the ``*_device`` forms run the
+same selection on the MI355X and give the same result, with the reference's
+call only where NumPy's own behaviour decides.  The plain functions take
+arrays so they are testable without a GPU.
 """
 
 from __future__ import annotations
@@ -24,6 +26,72 @@ def sampled_mask(scores: np.ndarray, num_edges: int, retention_ratio: float,
     selected = rng.choice(num_edges, size=num_keep, replace=False, p=probs)
     mask = np.zeros(num_edges, dtype=bool)
     mask[selected] = True
+    return mask
+
+
+def sampled_mask_rounds(scores: np.ndarray, num_edges: int, retention_ratio: float,
+                        seed: int = 42):
+    """sampled_mask with ``Generator.choice(replace=False, p=...)`` (NumPy 2.x) written
+    out: the executable specification of gs_sample_mask.  Returns ``(mask, rounds,
+    draws)``: the same mask, the rejection rounds run and the uint64s consumed.
+
+    Each round draws ``size - n_uniq`` doubles, zeroes the found entries of p,
+    rebuilds cdf = cumsum(p) / cumsum(p)[-1] and searches it (side='right'); the
+    distinct indices of a round are all new (the cdf is flat on a zeroed entry), so
+    their order does not matter for the mask.  Inputs on which ``choice`` raises are
+    passed to sampled_mask, so its exception surfaces."""
+    rng = np.random.default_rng(seed)
+    floor = 1e-8
+    s = np.nan_to_num(scores, nan=floor, posinf=floor, neginf=floor)
+    probs = np.maximum(s, floor)
+    with np.errstate(all="ignore"):
+        total = probs.sum() if len(probs) else 0.0
+        p = probs / total
+    num_keep = int(num_edges * retention_ratio)
+    if (num_edges < 1 or len(p) != num_edges or not 0 <= num_keep <= num_edges
+            or not np.isfinite(total)
+            or (p == 0).any()):
+        return sampled_mask(scores, num_edges, retention_ratio, seed), 0, 0
+    mask = np.zeros(num_edges, dtype=bool)
+    n_uniq = rounds = draws = 0
+    while n_uniq < num_keep:
+        x = rng.random(num_keep - n_uniq)
+        p[mask] = 0
+        cdf = np.cumsum(p)
+        cdf /= cdf[-1]
+        mask[cdf.searchsorted(x, side="right")] = True
+        rounds += 1
+        draws += len(x)
+        n_uniq = int(mask.sum())
+    return mask, rounds, draws
+
+
+def sampled_mask_device(engine, scores: np.ndarray, num_edges: int, retention_ratio: float,
+                        seed: int = 42, info: dict | None = None) -> np.ndarray:
+    """sampled_mask with the rounds of ``Generator.choice`` on the MI355X
+    (gs_sample_mask); the same mask, bit for bit.
+
+    Degenerate inputs (a non-finite total, a probability that underflowed to 0,
+    ``len(scores) != num_edges``, a keep count outside [0, E]) are those on which
+    NumPy raises or takes another branch: the device reports them and the
+    reference's own call is made, so its exception surfaces unchanged.
+
+    ``info`` (optional dict) receives ``path`` ("device" or "host"), ``rounds`` and
+    ``draws`` (uint64s of the PCG64 stream consumed)."""
+    if info is None:
+        info = {}
+    rng = np.random.default_rng(seed)  # before the scores, as the reference
+    raw = scores
+    scores = np.asarray(scores)
+    if scores.dtype != np.float64 or scores.ndim != 1:  # NumPy works in the scores' own dtype
+        info.update(path="host", rounds=0, draws=0)
+        return sampled_mask(raw, num_edges, retention_ratio, seed)
+    num_keep = int(num_edges * retention_ratio)
+    mask, status, rounds, draws = engine.sample_mask(scores, num_edges, num_keep, rng)
+    if status != 0:
+        info.update(path="host", rounds=0, draws=0)
+        return sampled_mask(scores, num_edges, retention_ratio, seed)
+    info.update(path="device", rounds=rounds, draws=draws)
     return mask
 
 

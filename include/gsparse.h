@@ -270,6 +270,42 @@ int gs_segment_topk(gs_ctx *ctx, const double *scores, int s_loc, int64_t nscore
                     int64_t *n_guaranteed, int64_t *n_ambiguous, int64_t *class_counts,
                     int ncounts);
 
+/* ---- sampling: GraphSparsifier.sparsify_sampled core.py:333-350 ------------
+ * mask[E] (uint8): the set rng.choice(E, size=num_keep, replace=False, p=probs)
+ * draws, bit for bit, with probs = maximum(nan_to_num(scores, 1e-8 for NaN and
+ * +-inf), 1e-8) / np.sum (the pairwise sums of NumPy's 8192-element buffer blocks,
+ * folded in order) and rng a Generator(PCG64) in the
+ * state (state_hi/lo, inc_hi/lo): NumPy 2.x's rejection rounds run on the device.
+ * Each round rebuilds cdf = cumsum(p) / cumsum(p)[-1] (sequential adds, IEEE
+ * divides) with the found entries of p zeroed, draws size - n_uniq doubles
+ * ((next_uint64 >> 11) * 2^-53), searches them (side='right') and claims the
+ * indices.  *rounds = rounds run, *draws = uint64s of the stream consumed (the
+ * generator's state afterwards is the given one advanced by *draws).
+ * *status: 0 = the mask was written by the device rounds; 1 = degenerate input,
+ * the mask is untouched: a total that is not finite and positive, a p that
+ * underflowed to 0, nscores != E, E < 1 or num_keep outside [0, E] -- NumPy
+ * raises or takes another branch on each, so the caller makes the reference's
+ * own call.  num_keep == 0: an all-zero mask, status 0, 0 rounds, 0 draws.
+ * Read-outs of the pieces (parity tests, the same kernels):
+ *   gs_pcg64_doubles   out[j] = Generator.random()'s double number offset + j of
+ *                      the stream, j < n.
+ *   gs_sample_probs    p_out[n] = the normalised probs above, *total_out = the sum
+ *                      they were divided by (n >= 1).
+ *   gs_cumsum_ordered  out[n] = np.cumsum(p) (not divided; out must not be p).
+ * GS_SAMPLE_TILE: elements per LDS tile of the ordered cumsum; GS_SAMPLE_SUBTREE:
+ * each block's pairwise tree is cut into subtrees of at most this many terms, one
+ * thread each (sizes around both are where the kernels change path). */
+enum { GS_SAMPLE_TILE = 1024, GS_SAMPLE_SUBTREE = 2048 };
+int gs_sample_mask(gs_ctx *ctx, const double *scores, int s_loc, int64_t nscores, int64_t E,
+                   int64_t num_keep, uint64_t state_hi, uint64_t state_lo, uint64_t inc_hi,
+                   uint64_t inc_lo, uint8_t *mask, int m_loc, int32_t *status, int64_t *rounds,
+                   int64_t *draws);
+int gs_pcg64_doubles(gs_ctx *ctx, uint64_t state_hi, uint64_t state_lo, uint64_t inc_hi,
+                     uint64_t inc_lo, uint64_t offset, int64_t n, double *out, int loc);
+int gs_sample_probs(gs_ctx *ctx, const double *scores, int s_loc, int64_t n, double *p_out,
+                    int loc, double *total_out);
+int gs_cumsum_ordered(gs_ctx *ctx, const double *p, int p_loc, int64_t n, double *out, int loc);
+
 int gs_metric_backbone(gs_ctx *ctx, int64_t n, int64_t E, const int64_t *src,
                        const int64_t *dst, const double *w, int64_t nw, int loc, double eps,
                        uint8_t *keep, int keep_loc, int64_t *n_relax);
