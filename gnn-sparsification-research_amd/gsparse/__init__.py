@@ -20,7 +20,7 @@ from .metrics import (
     compute_topology_metrics,
     compute_topology_preservation,
 )
-from .random import precompute_random_scores, random_sparsify
+from .random import RandomBaseline, precompute_random_scores, random_sparsify
 
 __all__ = [
     "GraphSparsifier",
@@ -39,4 +39,5 @@ __all__ = [
     "compute_topology_preservation",
     "precompute_random_scores",
     "random_sparsify",
+    "RandomBaseline",
 ]

@@ -76,6 +76,11 @@ SIGNATURES = {
     "gs_pcg64_doubles": (_int, [_vp, _u64, _u64, _u64, _u64, _u64, _i64, _vp, _int]),
     "gs_sample_probs": (_int, [_vp, _vp, _int, _i64, _vp, _int, ctypes.POINTER(_f64)]),
     "gs_cumsum_ordered": (_int, [_vp, _vp, _int, _i64, _vp, _int]),
+    "gs_undirected_ids": (_int, [_vp, _i64, _i64, _vp, _vp, _int, _vp, _int, ctypes.POINTER(_i64),
+                                 ctypes.POINTER(_i32)]),
+    "gs_random_mask": (_int, [_vp, _vp, _int, _i64, _i64, _vp, _int, _i64, _vp, _int,
+                              ctypes.POINTER(_f64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                              ctypes.POINTER(_i64)]),
     "gs_metric_backbone": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _int, _f64, _vp, _int,
                                   ctypes.POINTER(_i64)]),
     "gs_metric_backbone_part": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _int, _f64, _int,

@@ -474,12 +474,101 @@ class Engine:
             return None, status.value, 0, 0
         return mask[:num_edges].view(bool), 0, rounds.value, draws.value
 
-    def pcg64_doubles(self, rng: np.random.Generator, offset: int, n: int) -> np.ndarray:
-        """gs_pcg64_doubles: ``rng.random(offset + n)[offset:]`` drawn on the device."""
+    def pcg64_doubles(self, rng: np.random.Generator, offset: int, n: int, out=None):
+        """gs_pcg64_doubles: ``rng.random(offset + n)[offset:]`` drawn on the device
+        (into the CUDA float64 tensor ``out`` of >= n elements when given)."""
+        if out is not None:
+            import torch
+
+            self._need(out, n, (torch.float64,), "out")
+            if not out.is_cuda:
+                raise ValueError("out must be a CUDA float64 tensor")
+            self.ctx.call("gs_pcg64_doubles", *self._pcg64_words(rng), int(offset), int(n), ptr(out),
+                          GS_DEVICE)
+            return out
         out = np.empty(max(n, 1), dtype=np.float64)
         self.ctx.call("gs_pcg64_doubles", *self._pcg64_words(rng), int(offset), int(n), ptr(out),
                       GS_HOST)
         return out[:n]
+
+    # -- symmetric random baseline (gs_undirected_ids / gs_random_mask) ---------
+    @staticmethod
+    def _i64_input(a):
+        """A contiguous int64 numpy array or CUDA tensor, and where it lives."""
+        if isinstance(a, np.ndarray):
+            return np.ascontiguousarray(a, dtype=np.int64), GS_HOST
+        import torch
+
+        if a.dtype != torch.int64:
+            a = a.to(torch.int64)
+        if not a.is_cuda:
+            return np.ascontiguousarray(a.detach().numpy()), GS_HOST
+        return a.contiguous(), GS_DEVICE
+
+    def undirected_ids(self, src, dst, num_nodes: int, out=None):
+        """gs_undirected_ids: ``np.unique(keys, return_inverse=True)[1]`` of the undirected
+        keys ``min * (num_nodes + 1) + max`` (random.py:23-30).  ``src`` / ``dst``: int64
+        numpy arrays or CUDA tensors (both alike); ``out``: an optional CUDA int64 tensor
+        of >= E elements that receives the ids on the device.
+
+        Returns ``(inverse, n_undirected, status)``; status 1 = the input is outside the
+        device contract, nothing was written (``inverse`` is None) and the reference's own
+        NumPy calls decide."""
+        src, loc = self._i64_input(src)
+        dst, dloc = self._i64_input(dst)
+        if loc != dloc:
+            raise ValueError("src and dst must both be numpy arrays or both CUDA tensors")
+        E = int(src.shape[0])
+        if int(dst.shape[0]) != E:
+            raise ValueError(f"src holds {E} ids, dst {int(dst.shape[0])}")
+        if out is None:
+            inv, iloc = np.empty(max(E, 1), dtype=np.int64), GS_HOST
+        else:
+            import torch
+
+            self._need(out, E, (torch.int64,), "out")
+            if not out.is_cuda:
+                raise ValueError("out must be a CUDA int64 tensor of >= E elements")
+            inv, iloc = out, GS_DEVICE
+        cnt, status = ctypes.c_int64(0), ctypes.c_int32(1)
+        self.ctx.call("gs_undirected_ids", int(num_nodes), E, ptr(src), ptr(dst), loc, ptr(inv), iloc,
+                      ctypes.byref(cnt), ctypes.byref(status))
+        if status.value != 0:
+            return None, 0, status.value
+        return (inv[:E] if out is None else out), cnt.value, 0
+
+    def random_mask(self, scores, inverse, n_keep: int, num_edges: int, out=None):
+        """gs_random_mask: ``keep_undir[inverse]`` with ``keep_undir`` the ``n_keep`` highest
+        of ``scores`` (random.py:45-49).  ``scores`` (float64) and ``inverse`` (int64, >=
+        num_edges entries): numpy arrays or CUDA tensors; ``out``: an optional CUDA
+        uint8/bool tensor of >= num_edges elements that receives the mask on the device.
+
+        Returns ``(mask, cut, beyond, tied)`` as topk_mask does; IndexError when an
+        ``inverse`` entry is outside ``[-len(scores), len(scores))``, as NumPy raises."""
+        if isinstance(scores, np.ndarray):
+            scores, sloc = np.ascontiguousarray(scores, dtype=np.float64), GS_HOST
+        elif scores.is_cuda:
+            scores, sloc = scores.contiguous(), GS_DEVICE
+        else:
+            scores, sloc = np.ascontiguousarray(scores.numpy(), dtype=np.float64), GS_HOST
+        if str(scores.dtype) not in ("float64", "torch.float64"):
+            raise TypeError(f"scores must be float64, got {scores.dtype}")
+        inverse, iloc = self._i64_input(inverse)
+        m, E = int(scores.shape[0]), int(num_edges)
+        self._need(inverse, E, (inverse.dtype,), "inverse")
+        if out is None:
+            mask, mloc = np.zeros(max(E, 1), dtype=np.uint8), GS_HOST
+        else:
+            if not out.is_cuda or out.numel() < E or out.element_size() != 1:
+                raise ValueError("out must be a CUDA uint8/bool tensor of >= num_edges elements")
+            mask, mloc = out, GS_DEVICE
+        cut, nb, nt, bad = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self.ctx.call("gs_random_mask", ptr(scores), sloc, m, int(n_keep), ptr(inverse), iloc, E,
+                      ptr(mask), mloc, ctypes.byref(cut), ctypes.byref(nb), ctypes.byref(nt),
+                      ctypes.byref(bad))
+        if bad.value:
+            raise IndexError(f"{bad.value} index entries are out of bounds for axis 0 with size {m}")
+        return (mask[:E].view(bool) if out is None else out), cut.value, nb.value, nt.value
 
     def sample_probs(self, scores: np.ndarray):
         """gs_sample_probs: (probs, total) of sparsify_sampled's normalisation."""

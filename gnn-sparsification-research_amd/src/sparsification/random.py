@@ -1,3 +1,3 @@
 """``src.sparsification.random`` drop-in (reference random.py)."""
 
-from gsparse.random import precompute_random_scores, random_sparsify  # noqa: F401
+from gsparse.random import RandomBaseline, precompute_random_scores, random_sparsify  # noqa: F401

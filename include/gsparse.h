@@ -306,6 +306,34 @@ int gs_sample_probs(gs_ctx *ctx, const double *scores, int s_loc, int64_t n, dou
                     int loc, double *total_out);
 int gs_cumsum_ordered(gs_ctx *ctx, const double *p, int p_loc, int64_t n, double *out, int loc);
 
+/* ---- symmetric random baseline: random.py:14-52 ----------------------------
+ * gs_undirected_ids (precompute_random_scores, random.py:23-30): for column i,
+ * inverse[i] = the rank of key_i = min(src, dst) * (n + 1) + max(src, dst) among
+ * the distinct keys in ascending order, i.e. np.unique(keys, return_inverse=True)[1];
+ * *n_undirected = the number of distinct keys (random.py:30).  src / dst at loc,
+ * inverse at inv_loc (GS_HOST or GS_DEVICE).  *status: 0 = written; 1 = the input
+ * is outside the device contract (an id outside [0, n), n < 1, n >= 2^31 or
+ * E < 1) and nothing was written: the caller makes the reference's own calls, so
+ * odd inputs behave as NumPy does (the ValueError of inverse_idx.max() on an empty
+ * graph included).  One wait for the host, for the status and the count.  The
+ * scores of random.py:31-32, default_rng(seed).random(n_undirected), are
+ * gs_pcg64_doubles at offset 0 of the fresh generator's state.
+ * gs_random_mask (random_sparsify, random.py:45-49): keep_undir = the n_keep
+ * highest of the m scores on gs_topk_mask's keys and stable tie rule (n_keep >= m
+ * keeps all, as argsort[-n_keep:] does; n_keep < 1 is GS_EINVAL: the caller passes
+ * max(1, int(m * r)), random.py:46), held in the context; then mask[i] =
+ * keep_undir[inverse[i]], i < E, with NumPy's index rule: an entry in [-m, 0)
+ * wraps, any other entry outside [0, m) is counted in *n_bad (the mask is then
+ * unspecified; the reference raises IndexError).  cut / n_beyond / n_tied as
+ * gs_topk_mask returns them: 0 < n_keep - n_beyond < n_tied means np.argsort's
+ * own order decides inside the tie block. */
+int gs_undirected_ids(gs_ctx *ctx, int64_t n, int64_t E, const int64_t *src, const int64_t *dst,
+                      int loc, int64_t *inverse, int inv_loc, int64_t *n_undirected,
+                      int32_t *status);
+int gs_random_mask(gs_ctx *ctx, const double *scores, int s_loc, int64_t m, int64_t n_keep,
+                   const int64_t *inverse, int i_loc, int64_t E, uint8_t *mask, int m_loc,
+                   double *cut, int64_t *n_beyond, int64_t *n_tied, int64_t *n_bad);
+
 int gs_metric_backbone(gs_ctx *ctx, int64_t n, int64_t E, const int64_t *src,
                        const int64_t *dst, const double *w, int64_t nw, int loc, double eps,
                        uint8_t *keep, int keep_loc, int64_t *n_relax);
