@@ -146,7 +146,7 @@ struct ErState {
 
 struct gs_ctx;
 namespace gs {
-struct BbRun;  // the staged metric backbone's state (gs_backbone.hip)
+struct BbRun;  // the staged metric backbone's state (gs_bb.hpp)
 void project_rows(gs_ctx *c, int64_t e0, int64_t e1, const double *draw, int64_t kraw, int64_t col0,
                   int64_t col1, double sqrt_k);
 }  // namespace gs

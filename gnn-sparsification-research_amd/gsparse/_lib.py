@@ -94,6 +94,7 @@ SIGNATURES = {
     "gs_bb_search": (_int, [_vp, _i64, _i64, _int, _int]),
     "gs_bb_finish": (_int, [_vp, _vp, _int, ctypes.POINTER(_i64)]),
     "gs_bb_classes": (_int, [_vp, _int]),
+    "gs_bb_geometry": (_int, [_i64, _i64, _i32, _i32, _vp]),
     "gs_jsel_begin": (_int, [_vp, _int, _int, _vp, _int, _i64, _int, _vp, _vp, _int]),
     "gs_jsel_step": (_int, [_vp, _vp, ctypes.POINTER(_int)]),
     "gs_jsel_result": (_int, [_vp, ctypes.POINTER(_f64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),

@@ -80,6 +80,17 @@ def er_plan(n: int, lnnz: int, ncols: int, blas_threads: int) -> dict:
     return dict(zip(("mode", "cpl", "ru", "chunks"), o.tolist()))
 
 
+def bb_geometry(n: int, nsrc: int, nranks: int = 1, lpart: int = 0) -> dict:
+    """The numbers a metric backbone run of n nodes (E > 0) takes on rank lpart of nranks,
+    under the GSPARSE_BB_* variables as they are now (gs_bb_geometry; host code, no
+    device): K landmarks, whether their searches spread over the GPU and with how many
+    workgroups each (lm_W, 0 when this rank has no landmark), and for nsrc sources with
+    open columns the sources per workgroup, its threads, the batches and the slabs."""
+    o = np.zeros(7, dtype=np.int64)
+    _lib.check(_lib.lib().gs_bb_geometry(n, nsrc, nranks, lpart, ptr(o)), "gs_bb_geometry")
+    return dict(zip(("K", "lm_coop", "lm_W", "S", "threads", "nbatch", "slabs"), o.tolist()))
+
+
 class Engine:
     """Scorers over the graph resident in ``ctx``."""
 

@@ -374,6 +374,13 @@ int gs_bb_state_io(gs_ctx *ctx, uint8_t *state, int loc, int dir);
 int gs_bb_plan(gs_ctx *ctx, int64_t *nbatch);
 int gs_bb_search(gs_ctx *ctx, int64_t b0, int64_t b1, int part, int nparts);
 int gs_bb_finish(gs_ctx *ctx, uint8_t *keep, int keep_loc, int64_t *n_relax);
+/* The numbers the stages above take for n nodes (E > 0; with E = 0 a run has K = 0) on
+ * rank lpart of nranks, with the GSPARSE_BB_* variables as they are now: out = {K
+ * landmarks, 1 when their searches spread over the device, workgroups per landmark of
+ * that form (0: this rank has none), and for nsrc sources with open columns: sources
+ * per workgroup S, threads per workgroup, nbatch = ceil(nsrc / S), slabs = workgroups
+ * launched at most}.  Host code only: needs no context and no device. */
+int gs_bb_geometry(int64_t n, int64_t nsrc, int32_t nranks, int32_t lpart, int64_t out[7]);
 
 /* Decision classes of the metric backbone (a diagnostic: which exact rule decided each
  * column of metric_backbone.py:97-111's comparison).  gs_bb_classes(ctx, 1) makes the

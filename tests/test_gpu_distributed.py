@@ -339,7 +339,7 @@ def test_staged_backbone_parts_vs_one_gpu(gs, nparts):
 
 @pytest.mark.parametrize("nparts", [1, 3])
 def test_landmark_searches_spread_vs_one_workgroup(gs, nparts, monkeypatch):
-    """The landmark searches of gs_bb_begin spread over the GPU (k_lm_round: W
+    """The landmark searches of gs_bb_begin spread over the GPU (k_bb_lm_round: W
     workgroups per landmark, one launch per round) reach the labels and completeness
     flags of one workgroup per landmark bit for bit (R-MAT-17, Jaccard costs), for
     every part's landmarks l = part (mod nparts)."""

@@ -1011,7 +1011,7 @@ def test_backbone_near_far_order(gs, nearfar, monkeypatch):
 @pytest.mark.parametrize("order", ["asc", "desc"])
 @pytest.mark.parametrize("S", ["8", "16"])
 def test_backbone_reverse_columns_vs_oracle(gs, weights, order, S, monkeypatch):
-    """The reverse-column decisions of k_bb_sssp_multi (gs_backbone.hip
+    """The reverse-column decisions of k_bb_sssp_multi (gs_bb_multi.hpp
     bb_cross_decide) on weights that stress their margins: small integers (exact
     ties between an edge and a 2- or 3-edge path, where neither the prune nor the
     exact certificate may fire), costs over 18 decades (fl folds of very different

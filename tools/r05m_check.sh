@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: landmark searches spread over the GPU (k_lm_round) vs one workgroup per
+# GPU box: landmark searches spread over the GPU (k_bb_lm_round) vs one workgroup per
 # landmark: parity tests, then the staged backbone probe under both (RMAT-18).
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
