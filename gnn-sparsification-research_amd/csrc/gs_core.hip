@@ -208,10 +208,6 @@ void gs_destroy(gs_ctx *c) {
     c->outbuf.release();
     c->inbuf.release();
     c->inbuf2.release();
-    for (auto &a : c->aux)
-        if (a) (void)hipStreamDestroy(a);
-    for (auto &e : c->aux_ev)
-        if (e) (void)hipEventDestroy(e);
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     if (c->split_abort_ev) (void)hipEventDestroy(c->split_abort_ev);
     if (c->split_abort_host) (void)hipHostFree(c->split_abort_host);

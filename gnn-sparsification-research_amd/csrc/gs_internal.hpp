@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -82,8 +81,9 @@ struct ProfPending {
     double its_bytes = 0.0;
 };
 static constexpr int kProfPendingMax = 4096;
-// int32 entries allocated past the last column index: the Jaccard probe loop reads
-// lists in unconditional 64-lane steps (up to 511 entries past a list's end, masked)
+// int32 entries allocated past the last column index: the Jaccard probe loop takes a
+// list's tail in one masked step whose lanes past the end issue no load, but whose
+// addresses reach at most 63 entries past the list (the padding keeps them in bounds)
 static constexpr int64_t kIxPad = 1024;
 
 struct Graph {
@@ -98,16 +98,6 @@ struct Graph {
     DevBuf tpos;      // int64 [nnz] CSR position of each transposed entry
     bool has_transpose = false;
     int64_t epoch = 0;  // bumped whenever a new graph is set (keys the per-graph caches)
-};
-
-// Row ranges of the sharded Jaccard (gs_jaccard_shares): cuts = [R | E | O], P + 1
-// values each -- cut rows, their first CSR entries, owner entries before them
-struct JacShares {
-    std::vector<int64_t> cuts;
-    int P() const { return (int)(cuts.size() / 3) - 1; }
-    int64_t R(int r) const { return cuts[r]; }
-    int64_t E(int r) const { return cuts[P() + 1 + r]; }
-    int64_t O(int r) const { return cuts[2 * (P() + 1) + r]; }
 };
 
 struct ErState {
@@ -146,7 +136,8 @@ struct ErState {
 
 struct gs_ctx;
 namespace gs {
-struct BbRun;  // the staged metric backbone's state (gs_bb.hpp)
+struct BbRun;     // the staged metric backbone's state (gs_bb.hpp)
+struct JacState;  // the symmetric Jaccard's kept plan, shares and side streams (gs_jac.hpp)
 void project_rows(gs_ctx *c, int64_t e0, int64_t e1, const double *draw, int64_t kraw, int64_t col0,
                   int64_t col1, double sqrt_k);
 }  // namespace gs
@@ -155,8 +146,6 @@ struct gs_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
-    hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};  // side streams (Jaccard classes)
-    hipEvent_t aux_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t order_ev = nullptr;  // gs_stream_wait / gs_stream_signal (timing off)
     bool async_ = false;
     bool profiling = false;
@@ -165,20 +154,11 @@ struct gs_ctx {
     std::vector<gs::ProfPending> pending;
     gs::Graph g;
     gs::ErState er;
-    // symmetric Jaccard: the plan of the last call (graph epoch, part rows) kept with
-    // its task lists, so a repeated call plans nothing and does not wait for the host
-    std::vector<int64_t> jac_plan_key;
-    unsigned long long jac_plan_tot[8] = {};
-    std::vector<std::array<int64_t, 4>> jac_plan_bm;  // bitmap batches: g0, g1, task range
-    int64_t jac_bytes_epoch = -1;
-    double jac_bytes_sum = 0.0;
     std::vector<uint64_t> zig_key;  // (PCG64 state, stream length, block) of a parsed stream
     int64_t zig_draws = 0;          // draws known to cover it
     gs::DevBuf scratch[6];
     gs::DevBuf outbuf, inbuf, inbuf2;
     std::map<std::string, gs::DevBuf> named;  // per-subsystem buffers (backbone, ...)
-    std::map<int, gs::JacShares> jac_shares;  // sharded Jaccard row ranges, by part count
-    int64_t jac_epoch = -1;                   // graph epoch jac_shares belong to
     // register-resident CG (gs_cg_reg.hip): the ELL-8 copies are kept while their key
     // (graph epoch, L_reg shift, chunk / LDS layout) is unchanged; the split form is
     // switched off for the context after a hand-off gave up (its parts could not all
@@ -196,6 +176,7 @@ struct gs_ctx {
     int split_abort_parts = 0;
     int64_t split_aborts = 0;              // aborts seen by this context
     std::shared_ptr<gs::BbRun> bb;         // staged metric backbone (gs_bb_*)
+    std::shared_ptr<gs::JacState> jac;     // symmetric Jaccard (gs_jac*)
     gs::DevBuf &buf(const char *name) { return named[name]; }
 };
 
@@ -249,14 +230,6 @@ void ensure_transpose(gs_ctx *c);
 // Register-resident CG (ApproxER mode 5, gs_cg_reg.hip; the solvers' entry points are in
 // gs_cg.hpp): the abort word of its last split launch, read when the context goes away
 void split_abort_poll(gs_ctx *c, bool wait);
-
-// Whole-graph Jaccard of a symmetric graph (gs_jaccard.hip)
-// counts != 0: |N(u) ∩ N(v)| per entry instead of the Jaccard ratio
-// cc != nullptr: the part's raw counts into its compact owner-entry array
-void jaccard_symmetric(gs_ctx *c, double *out, int part, int nparts, int counts = 0,
-                       uint32_t *cc = nullptr);
-const JacShares &jaccard_shares(gs_ctx *c, int P);
-void jaccard_from_counts(gs_ctx *c, int P, const uint32_t *cc, int64_t stride, double *out);
 
 // Dense grounded-Laplacian machinery (gs_exact_er.hip): component labels of the
 // resident graph (smallest node id per component, device), and W = L^{-1} of

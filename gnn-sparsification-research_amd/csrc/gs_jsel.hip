@@ -21,7 +21,7 @@
 //   mask    every rank's codes -> the whole CSR keep mask (a gather through a per-entry
 //           code index cached per graph and part count)
 // The mask is bit-identical to gs_topk_mask on the gathered scores (the device tie rule).
-#include "gs_internal.hpp"
+#include "gs_jac.hpp"
 
 #include <map>
 #include <mutex>
@@ -284,10 +284,9 @@ extern "C" int gs_jsel_begin(gs_ctx *c, int part, int nparts, const uint32_t *co
         GS_HIP(hipMemsetAsync(hist, 0, sizeof(uint64_t) * kJselBins, s));
         hipEvent_t t0 = prof_begin(c);
         if (np) {
-            k_jsel_keys<<<grid_for(np, 256, 65536), 256, 0, s>>>(dc, c->buf("jac_opos").as<int32_t>(),
-                                                                c->buf("jac_orev").as<int32_t>(),
-                                                                c->buf("jac_osum").as<int32_t>(), H.obase, np,
-                                                                keys, wt, ds);
+            const JacOwners &own = jac_owners(c);
+            k_jsel_keys<<<grid_for(np, 256, 65536), 256, 0, s>>>(dc, own.opos, own.orev, own.osum, H.obase,
+                                                                np, keys, wt, ds);
             k_jsel_hist<<<grid_for(np, 256, 1024), 256, 0, s>>>(keys, wt, np, st, 0,
                                                                 (unsigned long long *)hist);
         }
@@ -338,7 +337,7 @@ extern "C" int gs_jsel_result(gs_ctx *c, double *cut, int64_t *n_beyond, int64_t
         auto *pos = (int64_t *)c->buf("jsel_tpos").ensure(sizeof(int64_t) * 2 * (H.npairs ? H.npairs : 1));
         if (H.npairs)
             k_jsel_ties<<<grid_for(H.npairs, 256, 2048), 256, 0, s>>>(
-                c->buf("jsel_keys").as<uint64_t>(), c->buf("jac_opos").as<int32_t>(), c->buf("jac_orev").as<int32_t>(),
+                c->buf("jsel_keys").as<uint64_t>(), jac_owners(c).opos, jac_owners(c).orev,
                 H.obase, H.npairs, st, pos);
         GS_HIP(hipGetLastError());
         JselDev h{};
@@ -397,7 +396,7 @@ extern "C" int gs_jsel_keep(gs_ctx *c, const int64_t *tie_pos, int64_t ntie, int
         hipEvent_t t0 = prof_begin(c);
         if (np)
             k_jsel_keep<<<grid_for(nb, 256, 65536), 256, 0, s>>>(
-                c->buf("jsel_keys").as<uint64_t>(), c->buf("jac_opos").as<int32_t>(), c->buf("jac_orev").as<int32_t>(),
+                c->buf("jsel_keys").as<uint64_t>(), jac_owners(c).opos, jac_owners(c).orev,
                 H.obase, np, (const JselDev *)c->buf("jsel_state").ptr, H.keep_lowest, mode, tall, ntie, need, dk);
         GS_HIP(hipGetLastError());
         prof_end(c, t0, "jsel_keep", 16.25 * (double)np);
@@ -428,7 +427,7 @@ extern "C" int gs_jsel_mask(gs_ctx *c, int nparts, const uint8_t *keep_all, int6
             GS_HIP(hipMemcpyAsync(dcut, sh.cuts.data(), sizeof(int64_t) * sh.cuts.size(), hipMemcpyHostToDevice, s));
             if (nown)
                 k_jsel_slots<<<grid_for(nown, 256, 65536), 256, 0, s>>>(
-                    c->buf("jac_opos").as<int32_t>(), c->buf("jac_orev").as<int32_t>(), dcut + 2 * (nparts + 1),
+                    jac_owners(c).opos, jac_owners(c).orev, dcut + 2 * (nparts + 1),
                     nparts, stride, nown, slot);
             GS_HIP(hipGetLastError());
             H.slot_key = key;

@@ -11,7 +11,7 @@
 // fp64 divide is IEEE (correctly rounded) on gfx950, so Jaccard is
 // bit-identical to the reference.  AA folds matches from the HIGH end so the
 // fp64 accumulation order equals SciPy csr_matmat's (see oracle.c).
-#include "gs_internal.hpp"
+#include "gs_jac.hpp"
 #include "gs_pairwise.hpp"
 
 #include <cstdlib>
@@ -237,10 +237,9 @@ int gs_jaccard(gs_ctx *c, int64_t e0, int64_t e1, double *out, int loc) {
         Graph &g = c->g;
         int64_t cnt = e1 - e0;
         double *dout = (double *)out_device(c, c->outbuf, out, sizeof(double) * cnt, loc);
-        const char *mode = getenv("GSPARSE_JACCARD");
-        const bool merge_only = mode && strcmp(mode, "merge") == 0;
-        if (cnt && g.symmetric && e0 == 0 && e1 == g.nnz && !merge_only) {
-            jaccard_symmetric(c, dout, 0, 1);  // owner-side hash/bitmap probing, both entries written
+        const JacKnobs knobs = jac_knobs();
+        if (cnt && g.symmetric && e0 == 0 && e1 == g.nnz && !knobs.merge_only) {
+            jaccard_symmetric(c, knobs, dout, 0, 1);  // owner-side hash/bitmap probing, both entries written
         } else if (cnt) {
             const int64_t *tp = g.symmetric ? g.indptr.as<int64_t>() : g.tptr.as<int64_t>();
             const int32_t *ti = g.symmetric ? g.indices.as<int32_t>() : g.tidx.as<int32_t>();
@@ -266,7 +265,7 @@ int gs_jaccard_part(gs_ctx *c, int part, int nparts, double *out, int loc) {
         const int64_t nnz = g.nnz;
         double *dout = (double *)out_device(c, c->outbuf, out, sizeof(double) * nnz, loc);
         if (nnz && g.symmetric) {
-            jaccard_symmetric(c, dout, part, nparts);
+            jaccard_symmetric(c, jac_knobs(), dout, part, nparts);
         } else if (nnz) {  // directed: this part's edge range, zeros elsewhere
             const int64_t e0 = nnz * part / nparts, e1 = nnz * (part + 1) / nparts;
             GS_HIP(hipMemsetAsync(dout, 0, sizeof(double) * nnz, c->stream));
@@ -279,54 +278,6 @@ int gs_jaccard_part(gs_ctx *c, int part, int nparts, double *out, int loc) {
                 prof_end(c, t0, "jaccard", 0.0);
             }
         }
-        finish_out(c, out, dout, sizeof(double) * nnz, loc);
-    });
-}
-
-static void check_sharded_jaccard(gs_ctx *c, int nparts) {
-    GS_CHECK(c, GS_EINVAL, "null context");
-    GS_CHECK(nparts >= 1 && nparts <= 4096, GS_EINVAL, "bad part count %d", nparts);
-    GS_CHECK(c->g.has_transpose, GS_ESTATE, "no graph set");
-    GS_CHECK(c->g.symmetric, GS_EUNSUPPORTED,
-             "owner-pair shares need a symmetric graph (use edge ranges on a directed one)");
-}
-
-int gs_jaccard_shares(gs_ctx *c, int nparts, int64_t *row_cut, int64_t *owner_off) {
-    return guard([&] {
-        check_sharded_jaccard(c, nparts);
-        GS_HIP(hipSetDevice(c->device));
-        const JacShares &sh = jaccard_shares(c, nparts);
-        for (int r = 0; r <= nparts; ++r) {
-            if (row_cut) row_cut[r] = sh.R(r);
-            if (owner_off) owner_off[r] = sh.O(r);
-        }
-    });
-}
-
-int gs_jaccard_part_counts(gs_ctx *c, int part, int nparts, uint32_t *counts, int loc) {
-    return guard([&] {
-        check_sharded_jaccard(c, nparts);
-        GS_CHECK(0 <= part && part < nparts, GS_EINVAL, "bad part %d of %d", part, nparts);
-        GS_HIP(hipSetDevice(c->device));
-        const JacShares &sh = jaccard_shares(c, nparts);
-        const int64_t cnt = sh.O(part + 1) - sh.O(part);
-        auto *d = (uint32_t *)out_device(c, c->outbuf, counts, sizeof(uint32_t) * cnt, loc);
-        if (cnt) jaccard_symmetric(c, nullptr, part, nparts, 0, d);
-        finish_out(c, counts, d, sizeof(uint32_t) * cnt, loc);
-    });
-}
-
-int gs_jaccard_from_counts(gs_ctx *c, int nparts, const uint32_t *counts, int64_t stride,
-                           int c_loc, double *out, int loc) {
-    return guard([&] {
-        check_sharded_jaccard(c, nparts);
-        GS_CHECK(stride >= 0, GS_EINVAL, "negative stride");
-        GS_HIP(hipSetDevice(c->device));
-        const int64_t nnz = c->g.nnz;
-        const uint32_t *dc = (const uint32_t *)to_device(c, c->inbuf, counts,
-                                                         sizeof(uint32_t) * stride * nparts, c_loc);
-        double *dout = (double *)out_device(c, c->outbuf, out, sizeof(double) * nnz, loc);
-        jaccard_from_counts(c, nparts, dc, stride, dout);
         finish_out(c, out, dout, sizeof(double) * nnz, loc);
     });
 }

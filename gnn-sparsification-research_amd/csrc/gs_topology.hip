@@ -18,7 +18,7 @@
 // Sturm-count bisection, all on the device.
 #include <cmath>
 
-#include "gs_internal.hpp"
+#include "gs_jac.hpp"
 
 namespace gs {
 
@@ -229,7 +229,7 @@ int gs_common_neighbors(gs_ctx *c, double *out, int loc) {
         GS_CHECK(g.symmetric, GS_EUNSUPPORTED, "common-neighbour counts need a symmetric graph");
         GS_HIP(hipSetDevice(c->device));
         double *dout = (double *)out_device(c, c->outbuf, out, sizeof(double) * (g.nnz ? g.nnz : 1), loc);
-        if (g.nnz) jaccard_symmetric(c, dout, 0, 1, 1);
+        if (g.nnz) jaccard_symmetric(c, jac_knobs(), dout, 0, 1, 1);
         finish_out(c, out, dout, sizeof(double) * g.nnz, loc);
     });
 }
@@ -248,7 +248,7 @@ int gs_clustering(gs_ctx *c, double *avg, double *per_node, int loc) {
                          ? per_node
                          : (double *)c->buf("topo_cv").ensure(sizeof(double) * (n ? n : 1));
         double *dav = (double *)c->buf("topo_avg").ensure(sizeof(double));
-        if (nnz) jaccard_symmetric(c, cnt, 0, 1, 1);
+        if (nnz) jaccard_symmetric(c, jac_knobs(), cnt, 0, 1, 1);
         if (n) {
             if (nnz)
                 k_clust_node<<<grid_for(n, 256, 8192), 256, 0, st>>>(g.indptr.as<int64_t>(), cnt, n,

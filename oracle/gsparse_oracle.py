@@ -114,7 +114,7 @@ def jaccard_counts(indptr, indices):
 
 
 def _jac_class(d):
-    """Degree classes of the device's owner-side Jaccard (gs_jaccard.hip)."""
+    """Degree classes of the device's owner-side Jaccard (gs_jac.hpp)."""
     d = np.asarray(d, dtype=np.int64)
     return np.select([d <= 32, d <= 1024, d <= 4096, d <= 8192, d <= 16384],
                      [-1, 0, 1, 2, 3], default=4)

@@ -367,7 +367,7 @@ def _column_costs(ei, n):
 
 
 def _hub_graph():
-    """RMAT-14 plus hubs in every Jaccard row class of gs_jaccard.hip (LDS tables
+    """RMAT-14 plus hubs in every Jaccard row class of gs_jac.hpp (LDS tables
     of 2K / 8K / 32K slots and the > 16384 bitmap rows), hub-hub edges and
     self-loops; symmetrised."""
     from gsparse import graphs
@@ -400,13 +400,11 @@ def test_jaccard_owner_hash_classes_vs_oracle(gs, monkeypatch):
     assert bits_equal(e.jaccard(), ref)
 
 
-@pytest.mark.parametrize("qdmax", [None, "0", "1"])
-@pytest.mark.parametrize("graph", ["hub60k", "spread3m"])
-def test_jaccard_quotient_tables_vs_oracle(gs, monkeypatch, graph, qdmax):
-    """The 16-bit quotient tables of row classes 1-3 (gs_jaccard.hip k_jac_hashq):
-    hubs in every class, ids of 16 bits (hub60k) and of 22 bits (spread3m: the
-    remainder width of RMAT-22), and -- GSPARSE_JAC_QDMAX -- the largest encodable
-    bucket distance cut to 0 / 1, so tasks overflow and probe the sorted list."""
+def _quotient_graph(graph):
+    """Hubs in every row class of the quotient tables, with shared leaves so that the
+    intersections are non-trivial: on the 60,000-node hub graph ("hub60k", ids of 16
+    bits) or alone on 3,000,000 nodes ("spread3m", ids of 22 bits: the remainder width of
+    RMAT-22); symmetrised.  Returns (edge_index, n)."""
     rng = np.random.default_rng(5)
     if graph == "hub60k":
         ei, n = _hub_graph()
@@ -425,6 +423,17 @@ def test_jaccard_quotient_tables_vs_oracle(gs, monkeypatch, graph, qdmax):
         hubs.append(np.stack([np.full(3000, hub), shared]))
     e2 = np.concatenate([ei, extra] + [h % n for h in hubs], axis=1)
     e2 = np.concatenate([e2, e2[::-1]], axis=1)
+    return e2, n
+
+
+@pytest.mark.parametrize("qdmax", [None, "0", "1"])
+@pytest.mark.parametrize("graph", ["hub60k", "spread3m"])
+def test_jaccard_quotient_tables_vs_oracle(gs, monkeypatch, graph, qdmax):
+    """The 16-bit quotient tables of row classes 1-3 (gs_jac_hash.hip k_jac_hashq):
+    hubs in every class, ids of 16 bits (hub60k) and of 22 bits (spread3m: the
+    remainder width of RMAT-22), and -- GSPARSE_JAC_QDMAX -- the largest encodable
+    bucket distance cut to 0 / 1, so tasks overflow and probe the sorted list."""
+    e2, n = _quotient_graph(graph)
     ip, ix, _ = O.canonical_csr(e2, n)
     deg = np.diff(ip)
     for lo, hi in [(1024, 4096), (4096, 8192), (8192, 16384)]:
