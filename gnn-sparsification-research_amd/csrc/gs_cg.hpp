@@ -4,6 +4,7 @@
 // (cg_plan: the only place that reads a GSPARSE_CG_* / GSPARSE_RES_* / GSPARSE_REG_*
 // variable) and the three solvers' entry points.
 #pragma once
+#include <algorithm>
 #include <climits>
 #include <cstddef>
 #include <cstdlib>
@@ -246,6 +247,102 @@ struct CgPlan {
 // len[t]) fit its thread geometry; reg_nt = 256 leaves only its 256-thread form
 bool cg_regres_applies(int64_t n, int T, const int64_t *len, int reg_nt);
 bool cg_regres_wide(int64_t n, int T, const int64_t *len, int reg_nt);  // its 512-thread form applies
+
+// ---------------------------------------------------------------- mode 5's LDS layout
+// Pure host code (gs_er_reg_layout exposes it; tests/test_er_reg_layout_host.py pins it).
+static constexpr int kRegLayoutChunks = 16;           // gs_cg_reg.hpp's kRegMaxChunks
+static constexpr size_t kRegLdsBytes = 160 * 1024;    // LDS of a CU
+
+// threads per chain for T chunks on an NT-thread workgroup (power of two, 32 T G <= NT,
+// G <= 8) and register row slots per thread (the chain rows); -1 when it does not apply
+inline int reg_geometry(int NT, int T, const int64_t *len, int &G) {
+    if (T < 1 || 32 * T > NT) return -1;
+    G = 1;
+    while (G < 8 && 32 * T * (2 * G) <= NT) G *= 2;
+    int64_t smax = 0;
+    for (int t = 0; t < T; ++t) smax = std::max<int64_t>(smax, (len[t] & ~(int64_t)31) >> 5);
+    return (int)((smax + G - 1) / G);
+}
+
+// workgroup size and slots: 512 threads (two waves per SIMD, k_cg_regwide) where the
+// slots fit 44, else 256 threads (one wave per SIMD, 512 registers per lane,
+// k_cg_regres) with up to 88.  reg_nt = 256 (the plan's, GSPARSE_REG_NT) forces the
+// one-wave form.
+inline bool reg_pick(int64_t n, int T, const int64_t *len, int reg_nt, int &NT, int &G, int &R) {
+    if (n <= 0 || n >= 0x8000) return false;
+    int g = 0;
+    const bool narrow_only = reg_nt == 256;
+    int r = narrow_only ? -1 : reg_geometry(512, T, len, g);
+    if (r >= 0 && r <= 44) {
+        NT = 512, G = g;
+        R = r <= 16 ? 16 : r <= 24 ? 24 : r <= 32 ? 32 : 44;
+        return true;
+    }
+    r = reg_geometry(256, T, len, g);
+    if (r < 0 || r > 88) return false;
+    NT = 256, G = g;
+    R = r <= 24 ? 24 : r <= 48 ? 48 : r <= 64 ? 64 : 88;
+    return true;
+}
+
+// Where p lives in a whole-column workgroup.  Chunk t keeps its first keep[t] rows (a
+// multiple of 32 G unless the whole chunk fits or GSPARSE_REG_KEEP caps it) in LDS from
+// slot lbase[t]; its other rows live in the workgroup's global slot.  After the prefixes:
+// the zero slot (zslot) and a scratch slot, dsl diagonal slots, 6 x 32 T doubles of chain
+// sums and tail rows, the chunk table.
+struct RegLayout {
+    int NT, G, R, T;
+    int64_t keep[kRegLayoutChunks], lbase[kRegLayoutChunks];
+    int64_t zslot;  // LDS slots of p
+    int dsl;        // diagonal slots
+    size_t dyn;     // LDS bytes of the launch
+};
+
+// ufast: the unit kernels that derive every diagonal from the entry count; reg_keep: the
+// most rows of a chunk kept in LDS (GSPARSE_REG_KEEP).  False when mode 5 does not apply.
+inline bool reg_layout(int64_t n, const ChunkArg &ch, int reg_nt, int64_t reg_keep, bool ufast,
+                       RegLayout &L) {
+    L = RegLayout{};
+    const int T = ch.count;
+    if (T > kRegLayoutChunks || !reg_pick(n, T, ch.len, reg_nt, L.NT, L.G, L.R)) return false;
+    L.T = T;
+    const int nch = 32 * T;
+    L.dsl = L.NT == 256 ? 2 * L.NT : ufast ? L.NT : 0;
+    const int64_t cap =
+        (int64_t)((kRegLdsBytes - (6 * (size_t)nch + 2 * kRegLayoutChunks + 2 + L.dsl) * 8) / 8);
+    // prefixes in proportion to the chunk lengths, whole wave-slots (32 G rows) when
+    // they cannot all fit
+    int64_t tot = 0;
+    for (int t = 0; t < T; ++t) tot += ch.len[t];
+    const int64_t align = 32 * L.G;
+    for (int t = 0; t < T; ++t)
+        L.keep[t] = tot <= cap ? ch.len[t] : (cap * ch.len[t] / tot) / align * align;
+    if (tot > cap) {
+        // the capacity the rounding left: one more wave-slot each for the chunks with the
+        // most rows outside LDS (Roman, 8 chunks: 7 x 64 more rows in LDS)
+        int64_t left = cap;
+        for (int t = 0; t < T; ++t) left -= L.keep[t];
+        while (left >= align) {
+            int best = -1;
+            for (int t = 0; t < T; ++t)
+                if (L.keep[t] + align <= ch.len[t] &&
+                    (best < 0 || ch.len[t] - L.keep[t] > ch.len[best] - L.keep[best]))
+                    best = t;
+            if (best < 0) break;
+            L.keep[best] += align;
+            left -= align;
+        }
+    }
+    for (int t = 0; t < T; ++t) L.keep[t] = std::min<int64_t>(L.keep[t], reg_keep);
+    int64_t zs = 0;
+    for (int t = 0; t < T; ++t) {
+        L.lbase[t] = zs;
+        zs += L.keep[t];
+    }
+    L.zslot = zs;
+    L.dyn = sizeof(double) * ((size_t)zs + 2 + L.dsl + 6 * (size_t)nch + 2 * kRegLayoutChunks);
+    return true;
+}
 
 // Pure host code.  The variables are read on every call: a process may change them
 // between solves.

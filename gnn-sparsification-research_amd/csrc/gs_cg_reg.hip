@@ -87,37 +87,7 @@ __global__ void k_ell8_fill(int32_t r0, int32_t n, int T, const int64_t *__restr
     }
 }
 
-// threads per chain for T chunks on an NT-thread workgroup (power of two, 32 T G <= NT,
-// G <= 8) and register row slots per thread (the chain rows); -1 when it does not apply
-static int reg_geometry(int NT, int T, const int64_t *len, int &G) {
-    if (T < 1 || 32 * T > NT) return -1;
-    G = 1;
-    while (G < 8 && 32 * T * (2 * G) <= NT) G *= 2;
-    int64_t smax = 0;
-    for (int t = 0; t < T; ++t) smax = std::max<int64_t>(smax, (len[t] & ~(int64_t)31) >> 5);
-    return (int)((smax + G - 1) / G);
-}
-
-// workgroup size and slots: 512 threads (two waves per SIMD, k_cg_regwide) where the
-// slots fit 44, else 256 threads (one wave per SIMD, 512 registers per lane,
-// k_cg_regres) with up to 88.  reg_nt = 256 (the plan's, GSPARSE_REG_NT) forces the
-// one-wave form.
-static bool reg_pick(int64_t n, int T, const int64_t *len, int reg_nt, int &NT, int &G, int &R) {
-    if (n <= 0 || n >= 0x8000) return false;
-    int g = 0;
-    const bool narrow_only = reg_nt == 256;
-    int r = narrow_only ? -1 : reg_geometry(512, T, len, g);
-    if (r >= 0 && r <= 44) {
-        NT = 512, G = g;
-        R = r <= 16 ? 16 : r <= 24 ? 24 : r <= 32 ? 32 : 44;
-        return true;
-    }
-    r = reg_geometry(256, T, len, g);
-    if (r < 0 || r > 88) return false;
-    NT = 256, G = g;
-    R = r <= 24 ? 24 : r <= 48 ? 48 : r <= 64 ? 64 : 88;
-    return true;
-}
+static_assert(kRegLayoutChunks == kRegMaxChunks, "reg_layout sizes its tables for kRegMaxChunks");
 
 bool cg_regres_applies(int64_t n, int T, const int64_t *len, int reg_nt) {
     int NT, G, R;
@@ -139,51 +109,24 @@ static void regres_run(gs_ctx *c, const CgPlan &plan, int64_t n, const int64_t *
     const int T = plan.ch.count;
     const int64_t *ha = plan.ch.a, *hlen = plan.ch.len;
     const int64_t slots = plan.slots;
-    int NT = 0, G = 0, rsel = 0;
-    GS_CHECK(reg_pick(n, T, hlen, plan.reg_nt, NT, G, rsel), GS_EUNSUPPORTED,
-             "register-resident CG: n=%lld, %d chunks out of range", (long long)n, T);
-    // LDS: p (each chunk's LDS-resident prefix, in chunk order), the zero and scratch
-    // slots, (one-wave form) 2 diagonal slots per thread, 6 x 32 T doubles of chain
-    // sums / tail rows, the chunk table
-    const int nch = 32 * T;
     const bool ufast = unit && dcount;  // the unit kernels derive every diagonal from the entry count
+    // LDS: p (each chunk's LDS-resident prefix, in chunk order), the zero and scratch
+    // slots, the diagonal slots, 6 x 32 T doubles of chain sums / tail rows, the chunk
+    // table (reg_layout, gs_cg.hpp)
+    RegLayout lay;
+    GS_CHECK(reg_layout(n, plan.ch, plan.reg_nt, plan.reg_keep, ufast, lay), GS_EUNSUPPORTED,
+             "register-resident CG: n=%lld, %d chunks out of range", (long long)n, T);
+    const int NT = lay.NT, G = lay.G, rsel = lay.R;
     // (512 threads, two per chain, unit: the diagonal slots bank-permuted -- the same
     // condition as k_cg_regwide's DBANK = GS_CG_V2 && UNIT && G == 2, so an A/B build with
     // -DGS_CG_V2=0 codes the diagonal where its kernel reads it)
     const bool dbank = GS_CG_V2 && NT == 512 && G == 2 && ufast;
-    const int dsl = NT == 256 ? 2 * NT : ufast ? NT : 0;
-    const size_t lds_max = 160 * 1024;
-    const int64_t cap =
-        (int64_t)((lds_max - (6 * (size_t)nch + 2 * kRegMaxChunks + 2 + dsl) * 8) / 8);
-    // prefixes in proportion to the chunk lengths, whole wave-slots (32 G rows) when
-    // they cannot all fit
-    int64_t keep[kRegMaxChunks], lbase[kRegMaxChunks], tot = 0;
-    for (int t = 0; t < T; ++t) tot += hlen[t];
-    const int64_t align = 32 * G;
-    for (int t = 0; t < T; ++t) keep[t] = tot <= cap ? hlen[t] : (cap * hlen[t] / tot) / align * align;
-    if (tot > cap) {
-        // the capacity the rounding left: one more wave-slot each for the chunks with the
-        // most rows outside LDS (Roman, 8 chunks: 7 x 64 more rows in LDS)
-        int64_t left = cap;
-        for (int t = 0; t < T; ++t) left -= keep[t];
-        while (left >= align) {
-            int best = -1;
-            for (int t = 0; t < T; ++t)
-                if (keep[t] + align <= hlen[t] && (best < 0 || hlen[t] - keep[t] > hlen[best] - keep[best])) best = t;
-            if (best < 0) break;
-            keep[best] += align;
-            left -= align;
-        }
-    }
-    for (int t = 0; t < T; ++t) keep[t] = std::min<int64_t>(keep[t], plan.reg_keep);
-    int64_t zs = 0;
-    for (int t = 0; t < T; ++t) {
-        lbase[t] = zs;
-        zs += keep[t];
-    }
+    const int dsl = lay.dsl;
+    const size_t lds_max = kRegLdsBytes;
+    const int64_t *keep = lay.keep, *lbase = lay.lbase;
+    const int64_t zs = lay.zslot;
     const uint32_t pad = (uint32_t)zs;  // the zero slot
-    const size_t dyn =
-        sizeof(double) * ((size_t)zs + 2 + dsl + 6 * (size_t)nch + 2 * kRegMaxChunks);
+    const size_t dyn = lay.dyn;
     // ELL-8 copy (uint16 p codes), overflow entries in CSR form: rebuilt only when the
     // graph, L_reg's shift or the chunk / LDS layout changed (the key)
     double regv = c->er.reg;

@@ -341,19 +341,49 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
 
     // V2 slot u (u >= 0): dg = L_reg_ii loaded, the global fix-up and the long-row tail
     // under the slot's mask bits; the arithmetic is spmv()'s, operation for operation
-    auto spmv2 = [&](int row, const uint4 e, double dg, double &pown, int u) -> double {
+    // own p of a row past the wave's LDS prefix, requested: its LDS slot and its row of the
+    // global slot (the code selects one when the value is used, so neither is waited for here)
+    auto next_own = [&](int row, double &pl, double &pgl) {
+        const int cd = code_of(row);
+        pl = spl[cd < 0x8000 ? cd : zslot];
+        pgl = __builtin_bit_cast(
+            double, __builtin_amdgcn_raw_buffer_load_b64(prs, cd < 0x8000 ? kOob : (cd & 0x7fff) * 8 + poff, 0, kAux));
+    };
+    // pnx / png: this slot's own p, requested by the slot before (by the pass for slot 0) --
+    // from LDS (pnx) for a slot of the prefix, from its code's LDS slot (pnx) and global row
+    // (png) for a slot past it -- and on return the next slot's.  A slot's -td is then
+    // ready when its ELL row is, and the own row of a slot past the prefix travels beside
+    // the previous slot's work instead of costing a memory round trip of its own.  The
+    // request follows the slot's gathers and precedes its overflow fold; the next slot's
+    // diagonal slot is written after both (a wave's LDS operations complete in order).
+    auto spmv2 = [&](int row, const uint4 e, double dg, double &pown, int u, double &pnx, double &png) -> double {
         const bool fast = u < ulds;  // wave-uniform
         const int self = fast ? 0 : code_of(row);
         const uint32_t w4[4] = {e.x, e.y, e.z, e.w};
         uint32_t ad[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) ad[k] = (k & 1) ? wide_code_addr<1>(w4[k >> 1]) : wide_code_addr<0>(w4[k >> 1]);
-        pown = fast ? lds_at(lds0() + 256u * G * u) : ldc(self);
+        if (!fast) {
+            const double ol = pnx, og = png;  // (values, not a select between the references)
+            pown = self < 0x8000 ? ol : og;
+        } else {
+            pown = pnx;
+        }
         const double td = dg * pown;
         spl[dslot] = -td;
         double pv[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) pv[k] = lds_at(ad[k]);
+        // the next slot's own p.  Requested for every lane that runs this slot: in a lane's
+        // last valid slot row + 32 G is a tail row, a row of the next chunk or a row >= n --
+        // its LDS code is bounded by the chunk's keep, a buffer offset past the global slot
+        // reads 0.0, an LDS address past the launch's allocation reads 0.0 (GSPARSE_REG_KEEP
+        // = 0), and the value is never used (the lane does not run slot u + 1).
+        // (The LDS read is unconditional and next_own replaces its result under the wave-
+        // uniform test: as the else-branch of that test it puts a branch into every slot of
+        // the prefix, 156 -> 164-172 ms per step on one box, profiles/r07_cg_ab/final2_*.)
+        if (u + 1 < R) pnx = lds_at(lds0() + 256u * G * (u + 1));
+        if (u + 1 < R && u + 1 >= ulds) next_own(row + 32 * G, pnx, png);
         uint64_t gm = gmask;  // tested here, not hoisted (see launder)
         asm volatile("" : "+s"(gm));
         if ((gm >> u) & 1) {
@@ -473,7 +503,11 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
     // chunks are summed in order from scalar reads (v_readlane), so the result is
     // wave-uniform without a broadcast
     auto finish = [&](const double *acc32all, const double *xa_all, const double *xb_all) -> double {
-        const int tq = lane >> 2, l = lane & 3;
+        // (laundered like the slot geometry: hoisted, the LDS addresses of the three finishes
+        // stay live across the whole column loop -- 4 -> 0 spilled VGPRs at 44 slots)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int tq = ln >> 2, l = ln & 3;
         const bool lv = tq < T;
         const int Lt = s_ch[kRegMaxChunks + (lv ? tq : 0)];
         const int n1 = Lt & ~15, n32t = n1 & ~31;
@@ -774,6 +808,11 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
                     if constexpr (V2) db[u] = diag_row(u);
                     else lb[u] = len_row(u);
                 }
+                double pnx = 0.0, png = 0.0;  // V2: own p of the next slot (spmv2)
+                if constexpr (V2) {
+                    pnx = lds_at(lds0());
+                    if (ulds <= 0) next_own(rowof(0), pnx, png);
+                }
 #pragma unroll
                 for (int u = 0; u < R; ++u) {
                     if (u + kPre < R) {
@@ -783,7 +822,7 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
                     }
                     double pv = 0.0, qv = 0.0;
                     if constexpr (V2) {
-                        if (valid(u)) qv = spmv2(rowof(u), eb[u], db[u], pv, u);
+                        if (valid(u)) qv = spmv2(rowof(u), eb[u], db[u], pv, u, pnx, png);
                     } else if (valid(u)) qv = spmv(rowof(u), eb[u], lb[u], pv, u);
                     if constexpr (QSX) q2store(u, qv);
                     else if constexpr (QR) qr[u] = qv;
@@ -915,6 +954,11 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
                     if constexpr (V2) db[u] = diag_row(u);
                     else lb[u] = len_row(u);
                 }
+                double pnx = 0.0, png = 0.0;
+                if constexpr (V2) {
+                    pnx = lds_at(lds0());
+                    if (ulds <= 0) next_own(rowof(0), pnx, png);
+                }
 #pragma unroll
                 for (int u = 0; u < R; ++u) {
                     if (u + kPre < R) {
@@ -924,7 +968,7 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
                     }
                     if (valid(u)) {
                         double pu;
-                        const double q = V2 ? spmv2(rowof(u), eb[u], db[u], pu, u)
+                        const double q = V2 ? spmv2(rowof(u), eb[u], db[u], pu, u, pnx, png)
                                             : spmv(rowof(u), eb[u], lb[u], pu, u);
                         const double t2 = alpha * q;
                         r[u] = r[u] - t2;

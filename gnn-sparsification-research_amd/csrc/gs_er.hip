@@ -434,6 +434,25 @@ int gs_er_plan(int64_t n, int64_t lnnz, int64_t ncols, int32_t blas_threads, int
     });
 }
 
+int gs_er_reg_layout(int64_t n, int32_t blas_threads, int32_t unit, int64_t out[72]) {
+    return guard([&] {
+        GS_CHECK(out, GS_EINVAL, "out is NULL");
+        GS_CHECK(n >= 0, GS_EINVAL, "negative size");
+        std::fill(out, out + 72, (int64_t)0);
+        const CgPlan plan = cg_plan(n, 0, 1, blas_threads);
+        RegLayout L;
+        if (!reg_layout(n, plan.ch, plan.reg_nt, plan.reg_keep, unit != 0, L)) return;
+        const int64_t head[8] = {L.NT, L.G, L.R, L.T, L.zslot, L.dsl, (int64_t)L.dyn, 0};
+        std::copy(head, head + 8, out);
+        for (int t = 0; t < L.T; ++t) {
+            out[8 + t] = plan.ch.a[t];
+            out[8 + 16 + t] = plan.ch.len[t];
+            out[8 + 32 + t] = L.keep[t];
+            out[8 + 48 + t] = L.lbase[t];
+        }
+    });
+}
+
 int gs_er_scores(gs_ctx *c, int64_t col0, int64_t col1, int64_t e0, int64_t e1, int finalize,
                  double *out, int loc) {
     return guard([&] {

@@ -80,6 +80,25 @@ def er_plan(n: int, lnnz: int, ncols: int, blas_threads: int) -> dict:
     return dict(zip(("mode", "cpl", "ru", "chunks"), o.tolist()))
 
 
+def er_reg_layout(n: int, blas_threads: int, unit: bool = True) -> dict | None:
+    """Where the register-resident solver (mode 5) keeps p for an n-row system, under
+    GSPARSE_REG_NT / GSPARSE_REG_KEEP as they are now (gs_er_reg_layout; host code, no
+    device); None where mode 5 does not apply.  threads per workgroup, G threads per
+    chain, R row slots per thread, T chunks, zslot (the LDS slots of p), dsl diagonal
+    slots, lds_bytes of a launch, and per chunk: start, len, its first keep rows in LDS
+    from LDS slot lbase."""
+    o = np.zeros(72, dtype=np.int64)
+    _lib.check(_lib.lib().gs_er_reg_layout(n, blas_threads, int(bool(unit)), ptr(o)),
+               "gs_er_reg_layout")
+    if o[0] == 0:
+        return None
+    d = dict(zip(("threads", "G", "R", "T", "zslot", "dsl", "lds_bytes"), o[:7].tolist()))
+    T = d["T"]
+    for i, name in enumerate(("start", "len", "keep", "lbase")):
+        d[name] = o[8 + 16 * i:8 + 16 * i + T].tolist()
+    return d
+
+
 def bb_geometry(n: int, nsrc: int, nranks: int = 1, lpart: int = 0) -> dict:
     """The numbers a metric backbone run of n nodes (E > 0) takes on rank lpart of nranks,
     under the GSPARSE_BB_* variables as they are now (gs_bb_geometry; host code, no

@@ -214,6 +214,15 @@ int gs_er_split(int64_t k, int32_t parts, int64_t *bounds);
  * GSPARSE_REG_* variables as they are now: out = {solver mode 0..5, columns per lane,
  * chain rows per trip, BLAS chunks}.  Host code only: needs no context and no device. */
 int gs_er_plan(int64_t n, int64_t lnnz, int64_t ncols, int32_t blas_threads, int32_t out[4]);
+/* Where the register-resident solver (mode 5) keeps p for an n-row system with
+ * blas_threads ddot threads, under GSPARSE_REG_NT / GSPARSE_REG_KEEP as they are now;
+ * unit: the unit-weight form whose diagonals follow from the entry counts.  out[0..7] =
+ * {threads per workgroup (0: mode 5 does not apply; the rest is then 0), threads per
+ * chain G, row slots per thread, BLAS chunks T, LDS slots of p (the zero slot's index),
+ * diagonal slots, LDS bytes of a launch, 0}; then four blocks of 16 per-chunk values:
+ * first row, rows, leading rows whose p is in LDS, LDS slot of the first row.  Host code
+ * only: needs no context and no device. */
+int gs_er_reg_layout(int64_t n, int32_t blas_threads, int32_t unit, int64_t out[72]);
 
 /* ---- selection: GraphSparsifier.sparsify core.py:229-242 -----------------
  * mask[E] (uint8): the num_keep highest (keep_lowest: lowest) of the nnz
