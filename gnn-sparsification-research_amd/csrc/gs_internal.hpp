@@ -231,11 +231,4 @@ void ensure_transpose(gs_ctx *c);
 // gs_cg.hpp): the abort word of its last split launch, read when the context goes away
 void split_abort_poll(gs_ctx *c, bool wait);
 
-// Dense grounded-Laplacian machinery (gs_exact_er.hip): component labels of the
-// resident graph (smallest node id per component, device), and W = L^{-1} of
-// M = L L^T for the grounded M (identity rows where flag[u], N x N scratch A, W)
-int32_t *components(gs_ctx *c);
-void grounded_inverse(gs_ctx *c, int64_t N, const uint8_t *flag, double *A, double *W);
-void transpose_square(gs_ctx *c, int64_t N, const double *W, double *U);
-
 }  // namespace gs

@@ -12,12 +12,13 @@
 //
 // Fiedler value: lambda_2(L) = 1 / lambda_max(L^+), L^+ = P G P with G the
 // grounded inverse (zero at the ground node) and P = I - 11^T / n; G x =
-// W^T (W x) with W = L_M^{-1} from gs_exact_er.hip's blocked Cholesky of the
-// grounded M.  lambda_max(P G P) by Lanczos with full (classical Gram-Schmidt,
+// W^T (W x) with W = L_M^{-1} from gs_chol.hip's blocked Cholesky of the
+// grounded M (gs_dense.hpp; the components are gs_components.hip's).  lambda_max(P G P) by Lanczos with full (classical Gram-Schmidt,
 // twice) reorthogonalisation; the tridiagonal's largest eigenvalue by
 // Sturm-count bisection, all on the device.
 #include <cmath>
 
+#include "gs_dense.hpp"
 #include "gs_jac.hpp"
 
 namespace gs {
@@ -40,24 +41,6 @@ __global__ void k_fold_mean(const double *__restrict__ cv, int64_t n, double *__
     double s = 0.0;
     for (int64_t v = 0; v < n; ++v) s = s + cv[v];
     out[0] = n ? s / (double)n : 0.0;
-}
-
-__global__ void k_comp_sizes(const int32_t *__restrict__ lab, int64_t n,
-                             unsigned long long *__restrict__ size) {
-    for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < n;
-         v += (int64_t)gridDim.x * blockDim.x)
-        atomicAdd(&size[lab[v]], 1ull);
-}
-
-__global__ void k_comp_stats(const int32_t *__restrict__ lab,
-                             const unsigned long long *__restrict__ size, int64_t n,
-                             unsigned long long *__restrict__ stats) {
-    for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < n;
-         v += (int64_t)gridDim.x * blockDim.x)
-        if (lab[v] == v) {
-            atomicAdd(&stats[0], 1ull);
-            atomicMax(&stats[1], size[v]);
-        }
 }
 
 // ---------------------------------------------------------------- Fiedler
@@ -273,23 +256,11 @@ int gs_components(gs_ctx *c, int32_t *labels, int loc, int64_t *count, int64_t *
         hipStream_t st = c->stream;
         const int64_t n = g.n;
         int32_t *lab = components(c);
-        auto *size = (unsigned long long *)c->buf("topo_size").ensure(8 * (n ? n : 1));
-        auto *stats = (unsigned long long *)c->buf("topo_stats").ensure(16);
-        GS_HIP(hipMemsetAsync(stats, 0, 16, st));
-        if (n) {
-            GS_HIP(hipMemsetAsync(size, 0, 8 * n, st));
-            k_comp_sizes<<<grid_for(n, 256, 8192), 256, 0, st>>>(lab, n, size);
-            k_comp_stats<<<grid_for(n, 256, 8192), 256, 0, st>>>(lab, size, n, stats);
-        }
-        unsigned long long h[2] = {0, 0};
-        GS_HIP(hipMemcpyAsync(h, stats, 16, hipMemcpyDeviceToHost, st));
         if (labels && n)
             GS_HIP(hipMemcpyAsync(labels, lab, 4 * n,
                                   loc == GS_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                                   st));
-        GS_HIP(hipStreamSynchronize(st));
-        if (count) *count = (int64_t)h[0];
-        if (largest) *largest = (int64_t)h[1];
+        component_stats(c, lab, count, largest);  // synchronises: the labels have landed too
     });
 }
 
@@ -307,31 +278,18 @@ int gs_fiedler(gs_ctx *c, double tol, int32_t max_iter, double *value, int32_t *
         GS_HIP(hipSetDevice(c->device));
         hipStream_t st = c->stream;
         int64_t ncomp = 0;
-        {
-            int32_t *lab = components(c);
-            auto *stats = (unsigned long long *)c->buf("topo_stats").ensure(16);
-            auto *size = (unsigned long long *)c->buf("topo_size").ensure(8 * n);
-            GS_HIP(hipMemsetAsync(stats, 0, 16, st));
-            GS_HIP(hipMemsetAsync(size, 0, 8 * n, st));
-            k_comp_sizes<<<grid_for(n, 256, 8192), 256, 0, st>>>(lab, n, size);
-            k_comp_stats<<<grid_for(n, 256, 8192), 256, 0, st>>>(lab, size, n, stats);
-            unsigned long long h[2];
-            GS_HIP(hipMemcpyAsync(h, stats, 16, hipMemcpyDeviceToHost, st));
-            GS_HIP(hipStreamSynchronize(st));
-            ncomp = (int64_t)h[0];
-        }
+        component_stats(c, components(c), &ncomp, nullptr);
         GS_CHECK(ncomp == 1, GS_EINVAL, "algebraic connectivity: graph has %lld components",
                  (long long)ncomp);
         // ground node 0 (any node grounds a connected graph); padding rows identity
-        const int64_t N = ((n + 63) / 64) * 64;
+        const int64_t N = dense_pad(n);
         auto *flag = (uint8_t *)c->buf("topo_flag").ensure(N);
         GS_HIP(hipMemsetAsync(flag, 0, N, st));
         GS_HIP(hipMemsetAsync(flag, 1, 1, st));
         if (N > n) GS_HIP(hipMemsetAsync(flag + n, 1, N - n, st));
-        const size_t mb = sizeof(double) * (size_t)N * (size_t)N;
-        double *A = (double *)c->buf("xer_X").ensure(mb);
-        double *W = (double *)c->buf("xer_S").ensure(mb);
-        grounded_inverse(c, N, flag, A, W);
+        const DenseScratch ds = dense_scratch(c, N);
+        double *A = ds.A, *W = ds.W;
+        grounded_inverse(c, xer_knobs(), N, flag, A, W);
         transpose_square(c, N, W, A);  // A = U = W^T: G x = U (W x)
         const int64_t ldv = (n + 63) & ~(int64_t)63;
         double *V = (double *)c->buf("lz_V").ensure(sizeof(double) * (size_t)(max_iter + 1) * ldv);

@@ -424,7 +424,9 @@ class Engine:
     # -- selection ------------------------------------------------------------
     def exact_er(self, out=None):
         """calculate_effective_resistance_scores (metrics.py:124-175) -- gs_exact_er:
-        dense fp64-MFMA Newton-Schulz inverse of L + sum_C J_C/|C|."""
+        the grounded Laplacian's inverse by a blocked fp64-MFMA Cholesky
+        (GSPARSE_XER_METHOD=ns: Newton-Schulz).  exact_er_iterations: 64-row blocks,
+        or the last Newton-Schulz step."""
         o, loc = self._out(0, self.nnz, out)
         it = ctypes.c_int32(0)
         self.ctx.call("gs_exact_er", ptr(o), loc, ctypes.byref(it))

@@ -95,9 +95,9 @@ def calculate_effective_resistance_scores(adj: sp.csr_matrix) -> NDArray[np.floa
     """EXACT effective resistance (metrics.py:124-175), dense, on the MI355X.
 
     The reference reads R(u,v) = P_uu + P_vv - 2 P_uv off pinv(L + 1e-10 I); this
-    reads it off inv(L + sum_C J_C/|C|) (equal in exact arithmetic for every
-    edge, whose endpoints share a component), inverted by Newton-Schulz on fp64
-    MFMA (gs_exact_er).  Agrees with the reference to its own pinv rounding
+    reads it off the inverse of L grounded at one node per component (equal in
+    exact arithmetic for every edge, whose endpoints share a component), by a
+    blocked Cholesky on fp64 MFMA (gs_exact_er).  Agrees with the reference to its own pinv rounding
     noise (<= 1e-4 relative on the fixtures; DESIGN.md §Exact ER).  Symmetric
     adjacency with n <= 32768 only (NotImplementedError otherwise)."""
     eng, perm = _engine(adj)

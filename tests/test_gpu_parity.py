@@ -9,6 +9,7 @@ identical keep masks for top-k (numpy tie mode), the metric backbone, the
 sampled and degree-aware selections.
 """
 
+import functools
 import os
 
 import numpy as np
@@ -776,9 +777,9 @@ def test_exact_er_kept_sets_vs_reference(gs, name):
                 assert np.array_equal(m[clear], rm[clear]), (name, r, low, int((m != rm)[clear].sum()))
 
 
-@pytest.mark.parametrize("n,blocks", [(3000, 5), (4100, 1), (70, 3)])
-def test_exact_er_components_and_padding(gs, n, blocks):
-    """Several components (plus isolated nodes), weights, n not a multiple of 64."""
+def _xer_parts_graph(n, blocks):
+    """Weighted symmetric CSR: `blocks` connected parts over nodes [0, n - 3), the last
+    three nodes isolated."""
     import scipy.sparse as sp
 
     rng = np.random.default_rng(n)
@@ -797,8 +798,65 @@ def test_exact_er_components_and_padding(gs, n, blocks):
     A = sp.coo_matrix((w, (r, c)), shape=(n, n)).tocsr()
     A = (A + A.T).tocsr()
     A.sum_duplicates()
-    er = gs.calculate_effective_resistance_scores(A)
+    return A
+
+
+@functools.lru_cache(maxsize=None)
+def _xer_parts_case(n, blocks):
+    """(graph, the lifted oracle's scores), computed once per shape and left unchanged."""
+    A = _xer_parts_graph(n, blocks)
     lifted = O.exact_er(A.indptr, A.indices, A.data, n, lifted=True)
+    lifted.setflags(write=False)
+    return A, lifted
+
+
+def _xer_engine(gs, A):
+    from gsparse._lib import Context
+
+    ctx = Context()
+    ctx.set_graph_csr(A.shape[0], A.indptr, A.indices, A.data)
+    return gs.engine.Engine(ctx)
+
+
+@pytest.mark.parametrize("n,blocks", [(3000, 5), (4100, 1), (70, 3)])
+def test_exact_er_components_and_padding(gs, n, blocks):
+    """Several components (plus isolated nodes), weights, n not a multiple of 64."""
+    A, lifted = _xer_parts_case(n, blocks)
+    er = gs.calculate_effective_resistance_scores(A)
+    np.testing.assert_allclose(er, lifted, rtol=1e-8, atol=1e-12)
+
+
+@pytest.mark.parametrize("panel", [1, 2, 3, 16])
+def test_exact_er_panel_widths(gs, monkeypatch, panel):
+    """The blocked Cholesky at every shape of its panel schedule.  n = 300 pads to
+    N = 320, five 64-blocks: GSPARSE_XER_PANEL=1 has no in-panel columns, 2 gives
+    panels of 2, 2, 1 (a short last one), 3 gives 3 + 2, and 16 exceeds the block
+    count, so no trailing update runs at all."""
+    A, lifted = _xer_parts_case(300, 2)
+    monkeypatch.setenv("GSPARSE_XER_PANEL", str(panel))
+    eng = _xer_engine(gs, A)
+    er = eng.exact_er()
+    assert eng.exact_er_iterations == 5
+    np.testing.assert_allclose(er, lifted, rtol=1e-8, atol=1e-12)
+
+
+@pytest.mark.parametrize("knobs", [{}, {"GSPARSE_XER_FULL": "1"}, {"GSPARSE_XER_TILE": "128"},
+                                   {"GSPARSE_XER_FULL": "1", "GSPARSE_XER_TILE": "128"}],
+                         ids=["sym", "full", "tile128", "full-tile128"])
+@pytest.mark.parametrize("n,blocks", [(70, 3), (300, 2)])
+def test_exact_er_newton_schulz(gs, monkeypatch, n, blocks, knobs):
+    """GSPARSE_XER_METHOD=ns: the Newton-Schulz inverse, in its upper-triangle form, with
+    every tile (GSPARSE_XER_FULL), and with GSPARSE_XER_TILE=128, which is taken at
+    N = 128 (n = 70: several grounds, isolated nodes, padding) and falls back to 64 at
+    N = 320 (n = 300).  k_dgemm<false, 128> needs both knobs at once, so the fourth
+    setting is there to make it all four k_dgemm forms."""
+    A, lifted = _xer_parts_case(n, blocks)
+    monkeypatch.setenv("GSPARSE_XER_METHOD", "ns")
+    for name, value in knobs.items():
+        monkeypatch.setenv(name, value)
+    eng = _xer_engine(gs, A)
+    er = eng.exact_er()
+    assert 0 < eng.exact_er_iterations < 255
     np.testing.assert_allclose(er, lifted, rtol=1e-8, atol=1e-12)
 
 
