@@ -15,11 +15,13 @@
 // W^T (W x) with W = L_M^{-1} from gs_chol.hip's blocked Cholesky of the
 // grounded M (gs_dense.hpp; the components are gs_components.hip's).  lambda_max(P G P) by Lanczos with full (classical Gram-Schmidt,
 // twice) reorthogonalisation; the tridiagonal's largest eigenvalue by
-// Sturm-count bisection, all on the device.
+// Sturm-count bisection (gs_lanczos.hpp), all on the device.  Above kFiedlerDenseMax
+// nodes gs_fiedler hands over to gs_fiedler_sparse.hip, which forms no dense matrix.
 #include <cmath>
 
 #include "gs_dense.hpp"
 #include "gs_jac.hpp"
+#include "gs_lanczos.hpp"
 
 namespace gs {
 
@@ -100,8 +102,7 @@ __global__ void __launch_bounds__(kLzThreads) k_lz_init(int64_t n, double *__res
     __shared__ double red[kLzWaves];
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += kLzThreads) {
-        const uint64_t h = ((uint64_t)i + 1) * 0x9E3779B97F4A7C15ull;
-        v[i] = (double)(h >> 11) * 0x1p-53 - 0.5;
+        v[i] = lz_start(i);
         s += v[i];
     }
     const double mean = lz_block_sum(s, red) / (double)n;
@@ -112,19 +113,6 @@ __global__ void __launch_bounds__(kLzThreads) k_lz_init(int64_t n, double *__res
     }
     const double nrm = sqrt(lz_block_sum(s, red));
     for (int64_t i = threadIdx.x; i < n; i += kLzThreads) v[i] /= nrm;
-}
-
-// Sturm count: eigenvalues of the (m x m) tridiagonal (a, b) below x
-__device__ int lz_sturm(const double *a, const double *b, int m, double x) {
-    int cnt = 0;
-    double q = 1.0;
-    for (int i = 0; i < m; ++i) {
-        const double bb = i ? b[i - 1] * b[i - 1] : 0.0;
-        q = a[i] - x - (i ? bb / q : 0.0);
-        if (q == 0.0) q = 1e-300;
-        if (q < 0.0) ++cnt;
-    }
-    return cnt;
 }
 
 // One Lanczos step on w = G x (the output of the two GEMVs): w <- P w,
@@ -181,19 +169,7 @@ __global__ void __launch_bounds__(kLzThreads) k_lz_step(int64_t n, int64_t ldv, 
         al[j] = a;
         be[j] = b;
         // largest eigenvalue of T (j+1 x j+1): Gershgorin bracket, bisection
-        const int m = j + 1;
-        double lo = 1e300, hi = -1e300;
-        for (int i = 0; i < m; ++i) {
-            const double r = (i ? fabs(be[i - 1]) : 0.0) + (i + 1 < m ? fabs(be[i]) : 0.0);
-            lo = fmin(lo, al[i] - r);
-            hi = fmax(hi, al[i] + r);
-        }
-        for (int it = 0; it < 200 && hi - lo > 1e-15 * fabs(hi); ++it) {
-            const double mid = 0.5 * (lo + hi);
-            if (lz_sturm(al, be, m, mid) < m) lo = mid;  // some eigenvalue above mid
-            else hi = mid;
-        }
-        theta[j] = hi;
+        theta[j] = lz_ritz_max(al, be, j + 1);
         c[0] = b;
     }
 }
@@ -272,9 +248,12 @@ int gs_fiedler(gs_ctx *c, double tol, int32_t max_iter, double *value, int32_t *
         GS_CHECK(g.symmetric, GS_EUNSUPPORTED, "algebraic connectivity needs a symmetric graph");
         const int64_t n = g.n;
         GS_CHECK(n >= 2, GS_EINVAL, "algebraic connectivity needs n >= 2");
-        GS_CHECK(n <= 32768, GS_EUNSUPPORTED, "algebraic connectivity here is dense O(n^3): n=%lld",
-                 (long long)n);
         GS_CHECK(max_iter >= 2 && max_iter <= 500, GS_EINVAL, "max_iter in [2, 500]");
+        if (n > kFiedlerDenseMax) {  // the dense form is O(n^3) and two n x n matrices
+            fiedler_sparse(c, tol, max_iter, kFiedlerCgRtol, kFiedlerCgMaxIter, value, iterations,
+                           nullptr);
+            return;
+        }
         GS_HIP(hipSetDevice(c->device));
         hipStream_t st = c->stream;
         int64_t ncomp = 0;

@@ -6,7 +6,7 @@ package does not touch the GPU; the first scorer call does, and fails loudly
 (``GsparseUnavailable``) when the HIP library or device is missing.
 """
 
-from ._lib import GsparseError, GsparseUnavailable
+from ._lib import GsparseError, GsparseNotConverged, GsparseUnavailable
 from .core import GraphSparsifier, SparsificationEngine
 from .data import Data
 from .metric_backbone import compute_metric_backbone
@@ -27,6 +27,7 @@ __all__ = [
     "SparsificationEngine",
     "Data",
     "GsparseError",
+    "GsparseNotConverged",
     "GsparseUnavailable",
     "compute_metric_backbone",
     "calculate_jaccard_scores",

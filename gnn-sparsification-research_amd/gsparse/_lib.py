@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("GSPARSE_LIB", os.path.join(_HERE, "libgsparse.so"))
 
 GS_HOST, GS_DEVICE = 0, 1
 GS_OK, GS_EINVAL, GS_EHIP, GS_ENOMEM, GS_ESTATE, GS_EUNSUPPORTED, GS_EINDEX = 0, -1, -2, -3, -4, -5, -6
+GS_ENOCONV = -7
 
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
@@ -111,6 +112,8 @@ SIGNATURES = {
     "gs_clustering": (_int, [_vp, ctypes.POINTER(_f64), _vp, _int]),
     "gs_components": (_int, [_vp, _vp, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "gs_fiedler": (_int, [_vp, _f64, _i32, ctypes.POINTER(_f64), ctypes.POINTER(_i32)]),
+    "gs_fiedler_sparse": (_int, [_vp, _f64, _i32, _f64, _i32, ctypes.POINTER(_f64),
+                                 ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
 }
 
 
@@ -126,6 +129,10 @@ class GsparseUnavailable(RuntimeError):
 
 class GsparseError(RuntimeError):
     pass
+
+
+class GsparseNotConverged(GsparseError):
+    """An iterative solver stopped at its cap unconverged (GS_ENOCONV): no value."""
 
 
 _LIB = None
@@ -166,6 +173,8 @@ def check(rc: int, what: str = ""):
         raise IndexError(text)
     if rc == GS_ENOMEM:
         raise MemoryError(text)
+    if rc == GS_ENOCONV:
+        raise GsparseNotConverged(f"[{rc}] {text}")
     raise GsparseError(f"[{rc}] {text}")
 
 

@@ -414,11 +414,36 @@ class Engine:
         self.ctx.call("gs_components", ptr(lab), GS_HOST, ctypes.byref(cnt), ctypes.byref(big))
         return lab[: self.n], cnt.value, big.value
 
-    def fiedler(self, tol: float = 1e-12, max_iter: int = 300):
-        """gs_fiedler: algebraic connectivity of the (connected) resident graph."""
-        v, it = ctypes.c_double(0.0), ctypes.c_int32(0)
-        self.ctx.call("gs_fiedler", float(tol), int(max_iter), ctypes.byref(v), ctypes.byref(it))
-        self.fiedler_iterations = it.value
+    def fiedler(self, tol: float = 1e-12, max_iter: int = 300, method: str = "auto",
+                cg_rtol: float = 1e-10, cg_max_iter: int = 5000):
+        """Algebraic connectivity of the (connected) resident graph.
+
+        method "auto": gs_fiedler (the dense Cholesky form up to 32768 nodes, the sparse
+        form with its default inner tolerances above); "dense": gs_fiedler on a graph the
+        dense form takes (NotImplementedError above 32768 nodes); "sparse":
+        gs_fiedler_sparse at any size, each Lanczos step a Jacobi-preconditioned CG solve
+        to relative residual cg_rtol within cg_max_iter iterations.  fiedler_iterations:
+        Lanczos steps; fiedler_cg_iterations: CG iterations of all solves of the last
+        method="sparse" call (None otherwise: gs_fiedler reports the steps only).  A solver that stops at a cap unconverged
+        raises GsparseNotConverged (a RuntimeError); the counts are recorded then too."""
+        if method not in ("auto", "dense", "sparse"):
+            raise ValueError(f"method must be 'auto', 'dense' or 'sparse', got {method!r}")
+        v, it, cg = ctypes.c_double(0.0), ctypes.c_int32(0), ctypes.c_int64(0)
+        self.fiedler_iterations = self.fiedler_cg_iterations = None
+        if method == "dense" and self.n > 32768:
+            raise NotImplementedError(f"the dense algebraic connectivity is O(n^3): n={self.n}")
+        try:
+            if method == "sparse":
+                self.ctx.call("gs_fiedler_sparse", float(tol), int(max_iter), float(cg_rtol),
+                              int(cg_max_iter), ctypes.byref(v), ctypes.byref(it),
+                              ctypes.byref(cg))
+            else:
+                self.ctx.call("gs_fiedler", float(tol), int(max_iter), ctypes.byref(v),
+                              ctypes.byref(it))
+        finally:
+            self.fiedler_iterations = it.value
+            if method == "sparse":
+                self.fiedler_cg_iterations = cg.value
         return v.value
 
     # -- selection ------------------------------------------------------------

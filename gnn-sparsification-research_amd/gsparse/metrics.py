@@ -245,9 +245,13 @@ def compute_topology_metrics(adj: sp.csr_matrix) -> Dict:
     degrees, clustering (``gs_clustering``, NetworkX's exact operation order) and
     components (``gs_components``) are exact; the algebraic connectivity of the
     graph (or of its largest component) is ``gs_fiedler`` -- 1 / lambda_max of the
-    Laplacian pseudo-inverse, Lanczos on an fp64-MFMA Cholesky inverse -- to
-    ~1e-10 relative where the reference's tracemin_lu stops at tol = 1e-8.
-    Dense: the largest component must have <= 32768 nodes."""
+    Laplacian pseudo-inverse by Lanczos, on an fp64-MFMA Cholesky inverse up to
+    32768 nodes and on Jacobi-preconditioned CG solves with the sparse Laplacian
+    above -- to ~1e-10 relative where the reference's tracemin_lu stops at
+    tol = 1e-8.  A solver that stops at an iteration cap unconverged raises
+    RuntimeError (``GsparseNotConverged``: the iteration counts and the residual
+    are in its message) where the reference would return whatever it had; no
+    value is made up."""
     n = adj.shape[0]
     S, loops, W = _nx_graph_arrays(adj)
     num_edges = int(S.nnz // 2 + np.count_nonzero(loops))

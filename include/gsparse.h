@@ -34,8 +34,10 @@ enum {
     GS_ENOMEM = -3,       /* device allocation failed                          */
     GS_ESTATE = -4,       /* call out of order (e.g. no graph set)             */
     GS_EUNSUPPORTED = -5, /* input outside the implemented contract            */
-    GS_EINDEX = -6        /* an array shorter than the index range it must cover
+    GS_EINDEX = -6,       /* an array shorter than the index range it must cover
                              (Python shim raises IndexError, as NumPy does)     */
+    GS_ENOCONV = -7       /* an iterative solver stopped at its cap unconverged;
+                             no value is returned (Python shim: RuntimeError)   */
 };
 
 enum { GS_HOST = 0, GS_DEVICE = 1 };
@@ -461,12 +463,28 @@ int gs_clustering(gs_ctx *ctx, double *avg, double *per_node, int per_loc);
  * of u's component (may be NULL), *count, *largest (size of the largest). */
 int gs_components(gs_ctx *ctx, int32_t *labels, int labels_loc, int64_t *count,
                   int64_t *largest);
-/* Algebraic connectivity (nx.algebraic_connectivity, weighted, unnormalised)
- * of a connected resident graph, n <= 32768: 1 / lambda_max(P G P), G the
- * grounded inverse of L (fp64-MFMA Cholesky), P = I - 11^T/n, by Lanczos with
- * full reorthogonalisation until the Ritz value changes by <= tol (relative)
- * or max_iter (<= 500) steps.  GS_EINVAL if the graph is not connected. */
+/* Algebraic connectivity (nx.algebraic_connectivity, weighted, unnormalised;
+ * metrics.py:478-510) of a connected resident graph: 1 / lambda_max(L^+) on the
+ * mean-free vectors (P = I - 11^T/n), by Lanczos with full reorthogonalisation
+ * until the Ritz value changes by <= tol (relative) or max_iter (<= 500)
+ * steps.  n <= 32768: the dense form, L^+ = P G P with G the grounded inverse of
+ * L (fp64-MFMA Cholesky).  Above: gs_fiedler_sparse with cg_rtol = 1e-10 and
+ * cg_max_iter = 5000.  GS_EINVAL if the graph is not connected. */
 int gs_fiedler(gs_ctx *ctx, double tol, int32_t max_iter, double *value, int32_t *iterations);
+/* The same value with no dense matrix, for a connected symmetric graph of any
+ * n >= 2 (the reference's tracemin_lu, metrics.py:478-510, has no size limit
+ * either): L^+ is applied by a CG solve of L y = P v_j on the mean-free
+ * vectors, Jacobi-preconditioned (the weighted degrees; stored diagonal entries
+ * are no part of L), to a relative residual cg_rtol within cg_max_iter
+ * iterations per solve.  Reductions are two-stage in a fixed order: two calls
+ * give the same bits.  GS_EINVAL for several components, GS_EUNSUPPORTED for a
+ * directed adjacency, GS_ENOCONV when a solve stops at cg_max_iter or Lanczos
+ * at max_iter unconverged: *value is then left untouched.  *iterations (outer
+ * steps) and *cg_iterations (inner iterations of all solves) are written in
+ * both cases; each may be NULL. */
+int gs_fiedler_sparse(gs_ctx *ctx, double tol, int32_t max_iter, double cg_rtol,
+                      int32_t cg_max_iter, double *value, int32_t *iterations,
+                      int64_t *cg_iterations);
 
 #ifdef __cplusplus
 }
