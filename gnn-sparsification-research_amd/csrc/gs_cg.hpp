@@ -241,6 +241,8 @@ struct CgPlan {
     int reg_split;           // GSPARSE_REG_SPLIT: 0 never, P >= 2 every column in P parts; -1 unset
     bool reg_split_auto;     // GSPARSE_REG_SPLIT_AUTO: two parts per tail column when they fit
     int32_t reg_split_spin;  // GSPARSE_REG_SPLIT_SPIN: a hand-off's wait budget; INT32_MIN unset
+    int reg_window;          // GSPARSE_REG_WINDOW: 0 never, 3 / 4 that window wherever the kernel
+                             // has one; -1 (unset): where it leaves fewer slow wave-slots
 };
 
 // Register-resident CG (mode 5, gs_cg_reg.hip): applies when the T BLAS chunks (lengths
@@ -290,54 +292,78 @@ inline bool reg_pick(int64_t n, int T, const int64_t *len, int reg_nt, int &NT, 
 // slot lbase[t]; its other rows live in the workgroup's global slot.  After the prefixes:
 // the zero slot (zslot) and a scratch slot, dsl diagonal slots, 6 x 32 T doubles of chain
 // sums and tail rows, the chunk table.
+// With a window (W > 0; two threads per chain, unit form) every chunk also owns W x 32 G
+// slots from wbase[t], between the prefixes and the zero slot: a rotating read-only cache
+// of the own p rows of the wave-slots around the one its wave works on (k_cg_regwide<WIN>).
 struct RegLayout {
     int NT, G, R, T;
     int64_t keep[kRegLayoutChunks], lbase[kRegLayoutChunks];
-    int64_t zslot;  // LDS slots of p
+    int64_t zslot;  // LDS slots of p (prefixes and windows)
     int dsl;        // diagonal slots
     size_t dyn;     // LDS bytes of the launch
+    int W;          // window size in wave-slots, 0: none
+    int64_t wbase[kRegLayoutChunks];
 };
 
 // ufast: the unit kernels that derive every diagonal from the entry count; reg_keep: the
-// most rows of a chunk kept in LDS (GSPARSE_REG_KEEP).  False when mode 5 does not apply.
+// most rows of a chunk kept in LDS (GSPARSE_REG_KEEP); win: the window asked for (3 or 4
+// wave-slots per chunk, reserved before the prefixes are apportioned; else none).  The
+// window kernel streams every row past the prefix from the global slot, so a window is
+// laid out only where it exists (512 threads, G == 2, unit) and every prefix is a whole
+// number of wave-slots; otherwise L.W == 0 and the layout is the plain one.  False when
+// mode 5 does not apply.
 inline bool reg_layout(int64_t n, const ChunkArg &ch, int reg_nt, int64_t reg_keep, bool ufast,
-                       RegLayout &L) {
+                       RegLayout &L, int win = 0) {
     L = RegLayout{};
     const int T = ch.count;
     if (T > kRegLayoutChunks || !reg_pick(n, T, ch.len, reg_nt, L.NT, L.G, L.R)) return false;
     L.T = T;
     const int nch = 32 * T;
     L.dsl = L.NT == 256 ? 2 * L.NT : ufast ? L.NT : 0;
-    const int64_t cap =
+    const int64_t cap0 =
         (int64_t)((kRegLdsBytes - (6 * (size_t)nch + 2 * kRegLayoutChunks + 2 + L.dsl) * 8) / 8);
-    // prefixes in proportion to the chunk lengths, whole wave-slots (32 G rows) when
-    // they cannot all fit
     int64_t tot = 0;
     for (int t = 0; t < T; ++t) tot += ch.len[t];
     const int64_t align = 32 * L.G;
-    for (int t = 0; t < T; ++t)
-        L.keep[t] = tot <= cap ? ch.len[t] : (cap * ch.len[t] / tot) / align * align;
-    if (tot > cap) {
-        // the capacity the rounding left: one more wave-slot each for the chunks with the
-        // most rows outside LDS (Roman, 8 chunks: 7 x 64 more rows in LDS)
-        int64_t left = cap;
-        for (int t = 0; t < T; ++t) left -= L.keep[t];
-        while (left >= align) {
-            int best = -1;
-            for (int t = 0; t < T; ++t)
-                if (L.keep[t] + align <= ch.len[t] &&
-                    (best < 0 || ch.len[t] - L.keep[t] > ch.len[best] - L.keep[best]))
-                    best = t;
-            if (best < 0) break;
-            L.keep[best] += align;
-            left -= align;
+    int W = ((win == 3 || win == 4) && L.NT == 512 && L.G == 2 && ufast) ? win : 0;
+    if (cap0 < (int64_t)T * W * align) W = 0;
+    for (;;) {
+        const int64_t cap = cap0 - (int64_t)T * W * align;
+        // prefixes in proportion to the chunk lengths, whole wave-slots (32 G rows) when
+        // they cannot all fit
+        for (int t = 0; t < T; ++t)
+            L.keep[t] = tot <= cap ? ch.len[t] : (cap * ch.len[t] / tot) / align * align;
+        if (tot > cap) {
+            // the capacity the rounding left: one more wave-slot each for the chunks with the
+            // most rows outside LDS (Roman, 8 chunks: 7 x 64 more rows in LDS)
+            int64_t left = cap;
+            for (int t = 0; t < T; ++t) left -= L.keep[t];
+            while (left >= align) {
+                int best = -1;
+                for (int t = 0; t < T; ++t)
+                    if (L.keep[t] + align <= ch.len[t] &&
+                        (best < 0 || ch.len[t] - L.keep[t] > ch.len[best] - L.keep[best]))
+                        best = t;
+                if (best < 0) break;
+                L.keep[best] += align;
+                left -= align;
+            }
         }
+        for (int t = 0; t < T; ++t) L.keep[t] = std::min<int64_t>(L.keep[t], reg_keep);
+        bool whole = true;
+        for (int t = 0; t < T; ++t) whole = whole && L.keep[t] % align == 0;
+        if (W == 0 || whole) break;
+        W = 0;  // a prefix ends inside a wave-slot: the plain layout
     }
-    for (int t = 0; t < T; ++t) L.keep[t] = std::min<int64_t>(L.keep[t], reg_keep);
     int64_t zs = 0;
     for (int t = 0; t < T; ++t) {
         L.lbase[t] = zs;
         zs += L.keep[t];
+    }
+    L.W = W;
+    for (int t = 0; t < T && W > 0; ++t) {
+        L.wbase[t] = zs;  // a multiple of 32 G: every prefix is
+        zs += W * align;
     }
     L.zslot = zs;
     L.dyn = sizeof(double) * ((size_t)zs + 2 + L.dsl + 6 * (size_t)nch + 2 * kRegLayoutChunks);
@@ -369,6 +395,8 @@ inline CgPlan cg_plan(int64_t n, int64_t lnnz, int64_t ncols, int32_t blas_threa
     p.reg_split = (e = getenv("GSPARSE_REG_SPLIT")) ? atoi(e) : -1;
     p.reg_split_auto = getenv("GSPARSE_REG_SPLIT_AUTO") != nullptr;
     p.reg_split_spin = (e = getenv("GSPARSE_REG_SPLIT_SPIN")) ? atoi(e) : INT32_MIN;
+    p.reg_window = -1;
+    if ((e = getenv("GSPARSE_REG_WINDOW"))) p.reg_window = atoi(e) == 3 ? 3 : atoi(e) == 4 ? 4 : 0;
 
     // two columns per lane (16-B accesses) unless that leaves too few waves
     const int64_t waves2 = ((ncols + 127) / 128) * 32 * (int64_t)ch.count;

@@ -24,13 +24,30 @@ __global__ void k_ell8_count(int32_t n, const int64_t *__restrict__ lp, int64_t 
 // p code of column c: its LDS slot when c is in its chunk's LDS-resident prefix,
 // else 0x8000 | c (chunk table: starts, lengths, prefixes, LDS bases).  A split part's
 // table holds only its own chunks: columns outside them are global (other parts' rows)
-__device__ __forceinline__ uint32_t p_code(int32_t c, int T, const int64_t *__restrict__ tab) {
+// Window (W > 0: two threads per chain, wave-slots of 64 rows, every prefix a whole number
+// of them; the table's fifth row holds the window bases): an entry of row i that names a
+// chain row c past the prefix of i's own chunk, at most one wave-slot from i's, with i a
+// chain row too, gets the LDS slot where the chunk's wave keeps c's p while it works on
+// i's slot -- position (slot(c) - prefix slots) mod W of the window, offset c's in its
+// wave-slot (k_cg_regwide<WIN>).  nwin counts these codes.
+__device__ __forceinline__ uint32_t p_code(int32_t c, int32_t i, int T, const int64_t *__restrict__ tab,
+                                           int W, int &nwin) {
     if (c < tab[0] || c >= tab[T - 1] + tab[kRegMaxChunks + T - 1]) return 0x8000u | (uint32_t)c;
     int t = 0;
     while (t + 1 < T && c >= tab[t + 1]) ++t;
-    const int64_t o = c - tab[t];
-    return o < tab[2 * kRegMaxChunks + t] ? (uint32_t)(tab[3 * kRegMaxChunks + t] + o)
-                                          : 0x8000u | (uint32_t)c;
+    const int64_t o = c - tab[t], keep = tab[2 * kRegMaxChunks + t];
+    if (o < keep) return (uint32_t)(tab[3 * kRegMaxChunks + t] + o);
+    if (W > 0) {
+        const int64_t oi = (int64_t)i - tab[t], n32 = tab[kRegMaxChunks + t] & ~(int64_t)31;
+        if (oi >= 0 && oi < n32 && o < n32) {
+            const int64_t sc = o >> 6, si = oi >> 6;
+            if (sc - si <= 1 && si - sc <= 1) {
+                ++nwin;
+                return (uint32_t)(tab[4 * kRegMaxChunks + t] + ((sc - (keep >> 6)) % W) * 64 + (o & 63));
+            }
+        }
+    }
+    return 0x8000u | (uint32_t)c;
 }
 
 // diagonal slot index of row c: 2 tid + parity in k_cg_regres (dmul 2), tid in
@@ -62,13 +79,15 @@ __global__ void k_ell8_fill(int32_t r0, int32_t n, int T, const int64_t *__restr
                             const int32_t *__restrict__ li, const double *__restrict__ lv,
                             const int64_t *__restrict__ optr, uint4 *__restrict__ ell,
                             double *__restrict__ ellv, uint16_t *__restrict__ ocol,
-                            double *__restrict__ oval, uint8_t *__restrict__ rflag) {
+                            double *__restrict__ oval, uint8_t *__restrict__ rflag, int W,
+                            unsigned long long *__restrict__ wcount) {
     for (int64_t i = r0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t e0 = lp[i], len = lp[i + 1] - e0;
         const uint32_t dcode = dslot0 >= 0 ? (uint32_t)(dslot0 + row_dslot((int32_t)i, T, tab, G, dmul, dslot0)) : 0u;
+        int nwin = 0;
         auto code = [&](int64_t e) -> uint32_t {
-            return (dslot0 >= 0 && li[e] == i) ? dcode : p_code(li[e], T, tab);
+            return (dslot0 >= 0 && li[e] == i) ? dcode : p_code(li[e], (int32_t)i, T, tab, W, nwin);
         };
         uint32_t w[4] = {0, 0, 0, 0};
         bool glob = false;
@@ -84,6 +103,22 @@ __global__ void k_ell8_fill(int32_t r0, int32_t n, int T, const int64_t *__restr
             ocol[optr[i] + k - 8] = (uint16_t)code(e0 + k);
             if (oval) oval[optr[i] + k - 8] = lv[e0 + k];
         }
+        if (wcount && nwin) atomicAdd(wcount, (unsigned long long)nwin);
+    }
+}
+
+// wave-slots (64 consecutive chain rows of a chunk, two threads per chain) with a global p
+// code among their rows' first 8 entries: the slots whose gathers k_cg_regwide's V2 form
+// fixes up from the global slot (its gmask)
+__global__ void k_reg_slow_slots(int T, const int64_t *__restrict__ tab, const uint8_t *__restrict__ rflag,
+                                 unsigned long long *__restrict__ out) {
+    const int t = blockIdx.x;
+    if (t >= T) return;
+    const int64_t a = tab[t], n32 = tab[kRegMaxChunks + t] & ~(int64_t)31;
+    for (int64_t u = threadIdx.x; u * 64 < n32; u += blockDim.x) {
+        bool any = false;
+        for (int64_t o = u * 64; o < n32 && o < u * 64 + 64; ++o) any = any || (rflag[a + o] & 1);
+        if (any) atomicAdd(out, 1ull);
     }
 }
 
@@ -110,30 +145,35 @@ static void regres_run(gs_ctx *c, const CgPlan &plan, int64_t n, const int64_t *
     const int64_t *ha = plan.ch.a, *hlen = plan.ch.len;
     const int64_t slots = plan.slots;
     const bool ufast = unit && dcount;  // the unit kernels derive every diagonal from the entry count
-    // LDS: p (each chunk's LDS-resident prefix, in chunk order), the zero and scratch
-    // slots, the diagonal slots, 6 x 32 T doubles of chain sums / tail rows, the chunk
-    // table (reg_layout, gs_cg.hpp)
-    RegLayout lay;
-    GS_CHECK(reg_layout(n, plan.ch, plan.reg_nt, plan.reg_keep, ufast, lay), GS_EUNSUPPORTED,
+    // LDS: p (each chunk's LDS-resident prefix, in chunk order; with a window, the chunks'
+    // windows), the zero and scratch slots, the diagonal slots, 6 x 32 T doubles of chain
+    // sums / tail rows, the chunk table (reg_layout, gs_cg.hpp)
+    RegLayout lay0, layw;
+    GS_CHECK(reg_layout(n, plan.ch, plan.reg_nt, plan.reg_keep, ufast, lay0), GS_EUNSUPPORTED,
              "register-resident CG: n=%lld, %d chunks out of range", (long long)n, T);
-    const int NT = lay.NT, G = lay.G, rsel = lay.R;
+    const int NT = lay0.NT, G = lay0.G, rsel = lay0.R;
+    // The p window (GSPARSE_REG_WINDOW; the whole-column unit kernel with two threads per
+    // chain only): unset, the default window is weighed against the plain layout when the
+    // ELL copy is rebuilt and used only if it leaves strictly fewer wave-slots with a global
+    // p code -- the count is the cost a window removes, and a graph without band locality
+    // keeps the plain layout and kernel; 3 / 4: that window wherever the kernel has one.
+    const int wask = !kRegWindowBuilt ? 0 : plan.reg_window < 0 ? kRegWindowDefault : plan.reg_window;
+    const bool have_w = wask > 0 && reg_layout(n, plan.ch, plan.reg_nt, plan.reg_keep, ufast, layw, wask) &&
+                        layw.W > 0;
     // (512 threads, two per chain, unit: the diagonal slots bank-permuted -- the same
     // condition as k_cg_regwide's DBANK = GS_CG_V2 && UNIT && G == 2, so an A/B build with
     // -DGS_CG_V2=0 codes the diagonal where its kernel reads it)
     const bool dbank = GS_CG_V2 && NT == 512 && G == 2 && ufast;
-    const int dsl = lay.dsl;
+    const int dsl = lay0.dsl;
     const size_t lds_max = kRegLdsBytes;
-    const int64_t *keep = lay.keep, *lbase = lay.lbase;
-    const int64_t zs = lay.zslot;
-    const uint32_t pad = (uint32_t)zs;  // the zero slot
-    const size_t dyn = lay.dyn;
     // ELL-8 copy (uint16 p codes), overflow entries in CSR form: rebuilt only when the
-    // graph, L_reg's shift or the chunk / LDS layout changed (the key)
+    // graph, L_reg's shift, the chunk / LDS layout or the window asked for changed (the key)
     double regv = c->er.reg;
     int64_t regbits;
     memcpy(&regbits, &regv, sizeof(regbits));
-    std::vector<int64_t> key = {c->g.epoch, regbits, n, T, G, NT, ufast ? 1 : 0, unit, dcount, dbank ? 1 : 0};
-    for (int t = 0; t < T; ++t) key.insert(key.end(), {ha[t], hlen[t], keep[t]});
+    std::vector<int64_t> key = {c->g.epoch, regbits, n, T, G, NT, ufast ? 1 : 0, unit, dcount, dbank ? 1 : 0,
+                                have_w ? layw.W : 0, plan.reg_window};
+    for (int t = 0; t < T; ++t) key.insert(key.end(), {ha[t], hlen[t], lay0.keep[t]});
     auto *ocnt = (int64_t *)c->buf("er_reg_ocnt").ensure(sizeof(int64_t) * (n + 1));
     auto *optr = (int64_t *)c->buf("er_reg_optr").ensure(sizeof(int64_t) * (n + 1));
     auto *rlen = (uint16_t *)c->buf("er_reg_rlen").ensure(sizeof(uint16_t) * n);
@@ -148,33 +188,70 @@ static void regres_run(gs_ctx *c, const CgPlan &plan, int64_t n, const int64_t *
         GS_HIP(hipStreamSynchronize(s));
     }
     const int64_t nov = c->reg_nov;
-    int64_t *dch;
-    {
-        c->reg_hch.assign(4 * kRegMaxChunks, 0);
-        int64_t *hch = c->reg_hch.data();
+    // chunk table: starts, lengths, prefixes, LDS bases, window bases
+    constexpr size_t kTabBytes = sizeof(int64_t) * 5 * kRegMaxChunks;
+    auto *dch = (int64_t *)c->buf("er_reg_chunks").ensure(kTabBytes);
+    auto upload = [&](const RegLayout &L, std::vector<int64_t> &host, int64_t *dev) {
+        host.assign(5 * kRegMaxChunks, 0);
         for (int t = 0; t < T; ++t) {
-            hch[t] = ha[t];
-            hch[kRegMaxChunks + t] = hlen[t];
-            hch[2 * kRegMaxChunks + t] = keep[t];
-            hch[3 * kRegMaxChunks + t] = lbase[t];
+            host[t] = ha[t];
+            host[kRegMaxChunks + t] = hlen[t];
+            host[2 * kRegMaxChunks + t] = L.keep[t];
+            host[3 * kRegMaxChunks + t] = L.lbase[t];
+            host[4 * kRegMaxChunks + t] = L.wbase[t];
         }
-        dch = (int64_t *)c->buf("er_reg_chunks").ensure(sizeof(int64_t) * 4 * kRegMaxChunks);
         // stream-ordered; the host table lives in the context until the next solve
-        GS_HIP(hipMemcpyAsync(dch, hch, sizeof(int64_t) * 4 * kRegMaxChunks, hipMemcpyHostToDevice, s));
-    }
+        GS_HIP(hipMemcpyAsync(dev, host.data(), kTabBytes, hipMemcpyHostToDevice, s));
+    };
     auto *ell = (uint4 *)c->buf("er_reg_ell").ensure(sizeof(uint4) * n);
     auto *rflag = (uint8_t *)c->buf("er_reg_rflag").ensure((size_t)n + 64);
     double *ellv = ufast ? nullptr : (double *)c->buf("er_reg_ellv").ensure(sizeof(double) * 8 * n);
     auto *ocol = (uint16_t *)c->buf("er_reg_ocol").ensure(sizeof(uint16_t) * (nov + 1));
     double *oval = ufast ? nullptr : (double *)c->buf("er_reg_oval").ensure(sizeof(double) * (nov + 1));
-    if (fresh) {
-        k_ell8_fill<<<grid_for(n, 256, 8192), 256, 0, s>>>(0, (int32_t)n, T, dch, pad, G,
+    auto fill = [&](const RegLayout &L, const int64_t *dev, unsigned long long *wcount) {
+        k_ell8_fill<<<grid_for(n, 256, 8192), 256, 0, s>>>(0, (int32_t)n, T, dev, (uint32_t)L.zslot, G,
                                                           NT == 256 ? 2 : dbank ? 3 : 1,
-                                                          ufast ? (int32_t)zs + 2 : -1,
-                                                          lp, li, lv, optr, ell, ellv, ocol, oval, rflag);
+                                                          ufast ? (int32_t)L.zslot + 2 : -1,
+                                                          lp, li, lv, optr, ell, ellv, ocol, oval, rflag, L.W,
+                                                          wcount);
         GS_HIP(hipGetLastError());
+    };
+    if (fresh && have_w) {
+        // both layouts' ELL copies in turn: the wave-slots with a global p code under each,
+        // the window codes; one wait, once per graph, beside the rebuild's own
+        auto *dch2 = (int64_t *)c->buf("er_reg_chunks2").ensure(kTabBytes);
+        auto *dcnt = (unsigned long long *)c->buf("er_reg_wcnt").ensure(sizeof(unsigned long long) * 3);
+        unsigned long long hcnt[3] = {0, 0, 0};
+        GS_HIP(hipMemsetAsync(dcnt, 0, sizeof(hcnt), s));
+        upload(lay0, c->reg_hch2, dch2);
+        fill(lay0, dch2, nullptr);
+        k_reg_slow_slots<<<T, 64, 0, s>>>(T, dch2, rflag, dcnt);
+        upload(layw, c->reg_hch, dch);
+        fill(layw, dch, dcnt + 2);
+        k_reg_slow_slots<<<T, 64, 0, s>>>(T, dch, rflag, dcnt + 1);
+        GS_HIP(hipGetLastError());
+        GS_HIP(hipMemcpyAsync(hcnt, dcnt, sizeof(hcnt), hipMemcpyDeviceToHost, s));
+        GS_HIP(hipStreamSynchronize(s));
+        const bool use_w = plan.reg_window > 0 || hcnt[1] < hcnt[0];
+        c->reg_win[0] = use_w ? layw.W : 0;
+        c->reg_win[1] = (int64_t)hcnt[0];
+        c->reg_win[2] = (int64_t)hcnt[1];
+        c->reg_win[3] = use_w ? (int64_t)hcnt[2] : 0;
+        if (!use_w) {
+            upload(lay0, c->reg_hch, dch);
+            fill(lay0, dch, nullptr);
+        }
+        c->reg_ell_key = key;
+    } else if (fresh) {
+        c->reg_win[0] = 0, c->reg_win[1] = c->reg_win[2] = -1, c->reg_win[3] = 0;
+        upload(lay0, c->reg_hch, dch);
+        fill(lay0, dch, nullptr);
         c->reg_ell_key = key;
     }
+    const RegLayout &lay = (have_w && c->reg_win[0] > 0) ? layw : lay0;
+    if (!fresh) upload(lay, c->reg_hch, dch);
+    const uint32_t pad = (uint32_t)lay.zslot;  // the zero slot
+    const size_t dyn = lay.dyn;
     RegArgs A{};
     // 512-thread form, whole columns: x in registers, q recomputed in the r update
     // (GSPARSE_REG_QR=1: q kept in registers from the SpMV pass, x read-modify-written
@@ -276,6 +353,8 @@ static void regres_run(gs_ctx *c, const CgPlan &plan, int64_t n, const int64_t *
     A.cl = dch + kRegMaxChunks;
     A.ck = dch + 2 * kRegMaxChunks;
     A.cb = dch + 3 * kRegMaxChunks;
+    A.cw = dch + 4 * kRegMaxChunks;
+    A.W = lay.W;
     A.prof = prof;
     // the whole-column launch (the first W columns); with a split tail it is issued
     // after the tail's tables and ELL are prepared, so the split launch follows it at once
@@ -343,7 +422,7 @@ static void regres_run(gs_ctx *c, const CgPlan &plan, int64_t n, const int64_t *
         const int32_t zsh = hpt[h * kRegPartTab + 4 * kRegMaxChunks + 1];
         k_ell8_fill<<<grid_for(r1 - r0, 256, 8192), 256, 0, s>>>(
             r0, r1, pc0[h + 1] - pc0[h], dtab + h * 4 * kRegMaxChunks, (uint32_t)zsh, Gs, 1,
-            ufast ? zsh + 2 : -1, lp, li, lv, optr, ells, ellvs, ocols, ovals, nullptr);
+            ufast ? zsh + 2 : -1, lp, li, lv, optr, ells, ellvs, ocols, ovals, nullptr, 0, nullptr);
         GS_HIP(hipGetLastError());
     }
     c->reg_split_key = skey;

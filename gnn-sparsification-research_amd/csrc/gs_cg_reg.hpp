@@ -97,7 +97,21 @@ struct RegArgs {
     const int32_t *gate;  // optional: solve the columns only if *gate != 0 (the whole-column
                           // re-solve of a split tail whose hand-offs gave up; read once at
                           // launch, wave-uniform), else every column as usual
+    // p window (k_cg_regwide<..., WIN>): W wave-slots per chunk from LDS slot cw[t]
+    int32_t W;
+    const int64_t *cw;
 };
+// the whole-column unit kernel with two threads per chain has a window form
+#ifndef GS_CG_QS
+#define GS_CG_QS 1
+#endif
+#ifndef GS_CG_XG
+#define GS_CG_XG 0
+#endif
+static constexpr bool kRegWindowBuilt = GS_CG_V2 && GS_CG_QS && !GS_CG_XG;
+// the window weighed when GSPARSE_REG_WINDOW is unset, in wave-slots (3 keeps one more
+// wave-slot per chunk in the prefix than 4)
+static constexpr int kRegWindowDefault = 3;
 static constexpr int kRegPartTab = 4 * kRegMaxChunks + 4;
 
 // A double held in two AGPRs.  r and x live there (read / written only through these

@@ -88,7 +88,16 @@ __device__ __forceinline__ double wide_readlane(double v, int ln) {
 // drained-sc1 recipe: sc1 payload, s_waitcnt vmcnt(0), barrier, one sc1 flag store, sc1
 // polls.  The chunk dots are added in global chunk order, so the bits are those of
 // the one-workgroup solve.  Used for the last, partly occupied round of columns.
-template <int G, int R, bool UNIT, bool QR, bool SPLIT = false>
+// WIN (V2, G == 2, q stored): each chunk -- one wave -- owns a rotating LDS window of A.W
+// wave-slots from slot A.cw[t], a read-only cache of the own p rows of the slots past the
+// prefix around the one being worked on.  Before the gathers of slot u are issued the
+// window holds the own p of every slot v with max(ulds, u - 1) <= v <= u + 1, so the ELL
+// codes of "a row one slot away in my own chunk" are LDS slots (k_ell8_fill) and the
+// slot needs no global fix-up.  The global slot stays the home of these rows: the p
+// update and the final x read it as in the plain form; the SpMV pass streams each slot's
+// own row from it two slots ahead (linear, coalesced), writes it to the window at the
+// start of the slot before its own, and uses the same register as that slot's own p.
+template <int G, int R, bool UNIT, bool QR, bool SPLIT = false, bool WIN = false>
 __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
     constexpr int CW = 64 / G;  // chains per wave
     // V2 (whole columns, unit weights): each slot's "any p code global" and "any row
@@ -105,6 +114,8 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
     constexpr bool QS = GS_CG_QS && !QR && !SPLIT;
     // (GS_CG_XG) whole columns in the x-in-Xc form with q stored, not kept in registers
     constexpr bool QSX = GS_CG_XG && QR && !SPLIT;
+    static_assert(!WIN || (V2 && G == 2 && QS),
+                  "the p window: whole columns, unit form, two threads per chain, q stored");
     extern __shared__ double lds[];
     const int part = SPLIT ? (int)(blockIdx.x % (unsigned)A.P) : 0;
     const int group = SPLIT ? (int)(blockIdx.x / (unsigned)A.P) : (int)blockIdx.x;
@@ -157,11 +168,16 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
     // keeps them live (hundreds of SGPRs/VGPRs, spilled to scratch).
     int ulds = 0;  // set below
     uint64_t gmask = 0, lmask = 0;  // V2 slot masks, set below
+    uint32_t wdelta = 0, wbytes = 0;  // WIN window geometry, set below
     auto launder = [&]() {
         asm volatile("" : "+v"(base), "+v"(uc), "+s"(ulds));
         if constexpr (V2) asm volatile("" : "+s"(gmask), "+s"(lmask));
+        if constexpr (WIN) asm volatile("" : "+s"(wdelta), "+s"(wbytes));
     };
-    const int ca_t = s_ch[t], keep_t = s_ch[2 * kRegMaxChunks + t], lbase_t = s_ch[3 * kRegMaxChunks + t];
+    // (WIN: a wave is one chunk, so its chunk's numbers are scalars)
+    auto chunk_num = [&](int v) { return WIN ? __builtin_amdgcn_readfirstlane(v) : v; };
+    const int ca_t = chunk_num(s_ch[t]), keep_t = chunk_num(s_ch[2 * kRegMaxChunks + t]),
+              lbase_t = chunk_num(s_ch[3 * kRegMaxChunks + t]);
     // slots u < ulds hold LDS-resident rows in every lane of the wave (a slot's rows are
     // 32 G consecutive rows of one chunk per lane group and the prefixes are whole
     // multiples of 32 G, so this is the wave's common prefix): their p lives at the
@@ -177,6 +193,13 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
         ulds = __builtin_amdgcn_readfirstlane(uk);
     }
     auto lds0 = [&]() -> uint32_t { return (uint32_t)(lbase_t + base - ca_t) * 8u; };
+    // WIN: a lane's byte address in window position 0 of its chunk is lds0() + wdelta (its
+    // rows sit at the same offset of every wave-slot; a wave is one chunk, so wdelta is
+    // wave-uniform); wbytes: the window's size
+    if constexpr (WIN) {
+        wdelta = (uint32_t)__builtin_amdgcn_readfirstlane(((int)A.cw[t] - lbase_t) * 8);
+        wbytes = (uint32_t)__builtin_amdgcn_readfirstlane(A.W * 256 * G);
+    }
     // explicit address spaces: a select between an LDS and a global pointer would
     // become one (slow) flat load
     typedef __attribute__((address_space(3))) double lds_f64;
@@ -385,6 +408,62 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
         if (u + 1 < R) pnx = lds_at(lds0() + 256u * G * (u + 1));
         if (u + 1 < R && u + 1 >= ulds) next_own(row + 32 * G, pnx, png);
         uint64_t gm = gmask;  // tested here, not hoisted (see launder)
+        asm volatile("" : "+s"(gm));
+        if ((gm >> u) & 1) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const bool gk = ad[k] >= 0x8000u * 8;
+                const double vg = __builtin_bit_cast(
+                    double, __builtin_amdgcn_raw_buffer_load_b64(prs, gk ? (int)(ad[k] & 0x3fff8u) + poff : kOob, 0, kAux));
+                pv[k] = gk ? vg : pv[k];
+            }
+            vm_drain();
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc = acc - pv[k];
+        uint64_t lm = lmask;
+        asm volatile("" : "+s"(lm));
+        if ((lm >> u) & 1) {  // rows longer than 8 entries: ocol
+            const int64_t o0 = A.optr[row], o1 = A.optr[row + 1];
+            for (int64_t q = o0; q < o1; ++q) acc = acc - ldc((int)A.ocol[q]);
+            vm_drain();
+        }
+        return acc;
+    };
+
+    // WIN: own p of the row `row` of a slot past the prefix, from its home in the global slot
+    // (rows past the chunk's chain rows read a neighbour's row, 0.0 past the slot or whatever
+    // lies between n and its end: such a value is written where no window code points and is
+    // the own p of a slot its lane does not run)
+    auto own_row = [&](int row) -> double {
+        return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(prs, row * 8, 0, kAux));
+    };
+    // WIN form of spmv2.  pc: this slot's own p; pn: slot u + 1's, requested by slot u - 1
+    // (by the pass for slots 0 and 1); on return pc is slot u + 1's and pn slot u + 2's,
+    // requested after this slot's gathers.  wa: the byte offset in the window (a whole
+    // number of wave-slots, kept by the pass) where slot u + 1's own p goes; it is written
+    // before the gathers -- a wave's LDS operations complete in order, so these gathers see
+    // slots u - 1 (W >= 3: its position is not the one overwritten), u and u + 1, and the
+    // gathers of slot u - 1, issued before the write, saw what they needed of slot u - 2.
+    auto spmv2w = [&](int row, const uint4 e, double dg, double &pown, int u, double &pc, double &pn,
+                      uint32_t wa) -> double {
+        const uint32_t w4[4] = {e.x, e.y, e.z, e.w};
+        uint32_t ad[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) ad[k] = (k & 1) ? wide_code_addr<1>(w4[k >> 1]) : wide_code_addr<0>(w4[k >> 1]);
+        if (u + 1 < R && u + 1 >= ulds) lds_put(lds0() + wdelta + wa, pn);  // wave-uniform
+        pown = pc;
+        const double td = dg * pown;
+        spl[dslot] = -td;
+        double pv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pv[k] = lds_at(ad[k]);
+        pc = pn;
+        // (the LDS read unconditional, as in spmv2: no branch in the slots of the prefix)
+        if (u + 2 < R) pn = lds_at(lds0() + 256u * G * (u + 2));
+        if (u + 2 < R && u + 2 >= ulds) pn = own_row(row + 64 * G);
+        uint64_t gm = gmask;
         asm volatile("" : "+s"(gm));
         if ((gm >> u) & 1) {
 #pragma unroll
@@ -809,7 +888,20 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
                     else lb[u] = len_row(u);
                 }
                 double pnx = 0.0, png = 0.0;  // V2: own p of the next slot (spmv2)
-                if constexpr (V2) {
+                uint32_t wq = 0;              // WIN: where the next own row goes in the window
+                if constexpr (WIN) {
+                    // the pass's prologue (every iteration: the window caches this iteration's
+                    // p): pnx / png are the own p of slots 0 and 1; without a prefix slot 0
+                    // enters the window here, before its own gathers
+                    pnx = lds_at(lds0());
+                    png = lds_at(lds0() + 256u * G);
+                    if (ulds <= 0) pnx = own_row(rowof(0));
+                    if (ulds <= 1) png = own_row(rowof(1));
+                    if (ulds <= 0) {
+                        if (valid(0)) lds_put(lds0() + wdelta, pnx);
+                        wq = 256u * G;
+                    }
+                } else if constexpr (V2) {
                     pnx = lds_at(lds0());
                     if (ulds <= 0) next_own(rowof(0), pnx, png);
                 }
@@ -821,7 +913,13 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
                         else lb[u + kPre] = len_row(u + kPre);
                     }
                     double pv = 0.0, qv = 0.0;
-                    if constexpr (V2) {
+                    if constexpr (WIN) {
+                        if (valid(u)) qv = spmv2w(rowof(u), eb[u], db[u], pv, u, pnx, png, wq);
+                        if (u + 1 < R && u + 1 >= ulds) {  // the position slot u + 1 took
+                            wq += 256u * G;
+                            wq = wq == wbytes ? 0u : wq;
+                        }
+                    } else if constexpr (V2) {
                         if (valid(u)) qv = spmv2(rowof(u), eb[u], db[u], pv, u, pnx, png);
                     } else if (valid(u)) qv = spmv(rowof(u), eb[u], lb[u], pv, u);
                     if constexpr (QSX) q2store(u, qv);
@@ -1043,6 +1141,18 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
         };                                                                                    \
         auto pick = [&](auto qr) {                                                            \
             constexpr bool Q = decltype(qr)::value;                                           \
+            if (A.W > 0) { /* the p window: built for two threads per chain, unit only */     \
+                if constexpr (!Q && G_ == 2 && kRegWindowBuilt) {                             \
+                    if (unit) {                                                               \
+                        if (R == 16) go(k_cg_regwide<G_, 16, true, Q, false, true>);          \
+                        else if (R == 24) go(k_cg_regwide<G_, 24, true, Q, false, true>);     \
+                        else if (R == 32) go(k_cg_regwide<G_, 32, true, Q, false, true>);     \
+                        else go(k_cg_regwide<G_, 44, true, Q, false, true>);                  \
+                        return;                                                               \
+                    }                                                                         \
+                }                                                                             \
+                GS_CHECK(false, GS_EUNSUPPORTED, "register-resident CG: no p window in this form"); \
+            }                                                                                 \
             if (unit) {                                                                       \
                 if (R == 16) go(k_cg_regwide<G_, 16, true, Q>);                               \
                 else if (R == 24) go(k_cg_regwide<G_, 24, true, Q>);                          \

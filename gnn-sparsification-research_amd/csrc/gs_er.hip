@@ -453,6 +453,40 @@ int gs_er_reg_layout(int64_t n, int32_t blas_threads, int32_t unit, int64_t out[
     });
 }
 
+// as gs_er_reg_layout with a p window of `window` wave-slots per chunk asked for (3 or 4;
+// laid out only where the window kernel exists, else the plain layout): out[7] the window
+// laid out (0: none), out[72 + t] its LDS base for chunk t
+int gs_er_reg_layout_w(int64_t n, int32_t blas_threads, int32_t unit, int32_t window, int64_t out[88]) {
+    return guard([&] {
+        GS_CHECK(out, GS_EINVAL, "out is NULL");
+        GS_CHECK(n >= 0, GS_EINVAL, "negative size");
+        std::fill(out, out + 88, (int64_t)0);
+        const CgPlan plan = cg_plan(n, 0, 1, blas_threads);
+        RegLayout L;
+        if (!reg_layout(n, plan.ch, plan.reg_nt, plan.reg_keep, unit != 0, L, window)) return;
+        const int64_t head[8] = {L.NT, L.G, L.R, L.T, L.zslot, L.dsl, (int64_t)L.dyn, L.W};
+        std::copy(head, head + 8, out);
+        for (int t = 0; t < L.T; ++t) {
+            out[8 + t] = plan.ch.a[t];
+            out[8 + 16 + t] = plan.ch.len[t];
+            out[8 + 32 + t] = L.keep[t];
+            out[8 + 48 + t] = L.lbase[t];
+            out[8 + 64 + t] = L.wbase[t];
+        }
+    });
+}
+
+// The p window of the last register-resident solve's ELL copy: its size in wave-slots (0:
+// the plain layout), the wave-slots with a global p code under the plain and the windowed
+// layout (-1 where no window was weighed), the window codes in the copy
+int gs_er_reg_window(gs_ctx *c, int64_t out[4]) {
+    return guard([&] {
+        GS_CHECK(c, GS_EINVAL, "null context");
+        GS_CHECK(out, GS_EINVAL, "out is NULL");
+        std::copy(c->reg_win, c->reg_win + 4, out);
+    });
+}
+
 int gs_er_scores(gs_ctx *c, int64_t col0, int64_t col1, int64_t e0, int64_t e1, int finalize,
                  double *out, int loc) {
     return guard([&] {

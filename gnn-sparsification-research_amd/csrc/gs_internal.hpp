@@ -166,6 +166,11 @@ struct gs_ctx {
     std::vector<int64_t> reg_ell_key, reg_split_key;
     int64_t reg_nov = 0;
     std::vector<int64_t> reg_hch;  // host copy of the chunk table (outlives its async copy)
+    std::vector<int64_t> reg_hch2; // ... of the other layout's while a window is weighed
+    // the p window the ELL copy was built with (gs_er_reg_window): its size in wave-slots,
+    // the wave-slots with a global p code under the plain and the windowed layout (-1: not
+    // counted), the window codes in the ELL copy
+    int64_t reg_win[4] = {0, -1, -1, 0};
     bool reg_split_off = false;
     int64_t reg_split_off_epoch = -1;      // graph epoch the split form was turned off for
     std::vector<int32_t> reg_split_hpt;    // host copies of the split tables (outlive their

@@ -68,6 +68,8 @@ SIGNATURES = {
     "gs_er_split": (_int, [_i64, _i32, _vp]),
     "gs_er_plan": (_int, [_i64, _i64, _i64, _i32, _vp]),
     "gs_er_reg_layout": (_int, [_i64, _i32, _i32, _vp]),
+    "gs_er_reg_layout_w": (_int, [_i64, _i32, _i32, _i32, _vp]),
+    "gs_er_reg_window": (_int, [_vp, _vp]),
     "gs_topk_mask": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _int,
                             ctypes.POINTER(_f64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "gs_segment_argmax": (_int, [_vp, _vp, _int, _i64, _vp, _int, _i64, _i64, _vp, _int]),

@@ -99,6 +99,24 @@ def er_reg_layout(n: int, blas_threads: int, unit: bool = True) -> dict | None:
     return d
 
 
+def er_reg_layout_w(n: int, blas_threads: int, window: int, unit: bool = True) -> dict | None:
+    """er_reg_layout with a p window of ``window`` wave-slots per chunk asked for (3 or 4;
+    gs_er_reg_layout_w): also W, the window laid out -- 0 where the window kernel does
+    not exist (other than two threads per chain, weighted) or a prefix is not a whole
+    number of wave-slots, and the layout is then er_reg_layout's -- and per chunk wbase,
+    the LDS slot its window starts at."""
+    o = np.zeros(88, dtype=np.int64)
+    _lib.check(_lib.lib().gs_er_reg_layout_w(n, blas_threads, int(bool(unit)), int(window), ptr(o)),
+               "gs_er_reg_layout_w")
+    if o[0] == 0:
+        return None
+    d = dict(zip(("threads", "G", "R", "T", "zslot", "dsl", "lds_bytes", "W"), o[:8].tolist()))
+    T = d["T"]
+    for i, name in enumerate(("start", "len", "keep", "lbase", "wbase")):
+        d[name] = o[8 + 16 * i:8 + 16 * i + T].tolist()
+    return d
+
+
 def bb_geometry(n: int, nsrc: int, nranks: int = 1, lpart: int = 0) -> dict:
     """The numbers a metric backbone run of n nodes (E > 0) takes on rank lpart of nranks,
     under the GSPARSE_BB_* variables as they are now (gs_bb_geometry; host code, no
@@ -365,6 +383,15 @@ class Engine:
         it = np.empty(self.k, dtype=np.int32)
         self.ctx.call("gs_er_iterations", ptr(it), GS_HOST)
         return it
+
+    def er_reg_window(self) -> dict:
+        """What the last register-resident solve (mode 5) chose for its p window
+        (gs_er_reg_window): W wave-slots per chunk (0: the plain layout), the wave-slots
+        with a global p code under the plain and under the windowed layout (-1 where no
+        window was weighed) and the window codes in the ELL copy."""
+        o = np.zeros(4, dtype=np.int64)
+        self.ctx.call("gs_er_reg_window", ptr(o))
+        return dict(zip(("W", "slow_plain", "slow_window", "window_codes"), o.tolist()))
 
     def er_z(self, col0: int, col1: int) -> np.ndarray:
         """The solved Z columns [col0, col1) as an (n, col1 - col0) array (gs_er_copy_z)."""

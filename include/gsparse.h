@@ -226,6 +226,19 @@ int gs_er_plan(int64_t n, int64_t lnnz, int64_t ncols, int32_t blas_threads, int
  * only: needs no context and no device. */
 int gs_er_reg_layout(int64_t n, int32_t blas_threads, int32_t unit, int64_t out[72]);
 
+/* As gs_er_reg_layout with a p window of `window` wave-slots per chunk asked for (3 or 4):
+ * out[7] = the window laid out -- 0 where the window kernel does not exist (other than
+ * two threads per chain; the weighted form) or a prefix is not a whole number of
+ * wave-slots, and the layout is then gs_er_reg_layout's -- and a fifth block of 16: the
+ * LDS slot each chunk's window starts at. */
+int gs_er_reg_layout_w(int64_t n, int32_t blas_threads, int32_t unit, int32_t window, int64_t out[88]);
+
+/* What the last register-resident solve chose for its p window (GSPARSE_REG_WINDOW):
+ * out = {window in wave-slots (0: the plain layout), wave-slots with a global p code
+ * under the plain layout, under the windowed one (-1 each where no window was weighed),
+ * window codes in the ELL copy}. */
+int gs_er_reg_window(gs_ctx *c, int64_t out[4]);
+
 /* ---- selection: GraphSparsifier.sparsify core.py:229-242 -----------------
  * mask[E] (uint8): the num_keep highest (keep_lowest: lowest) of the nnz
  * scores, ties broken as np.argsort(kind='stable') does (top: highest
