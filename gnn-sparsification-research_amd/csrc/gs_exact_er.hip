@@ -13,7 +13,9 @@
 // G by the blocked Cholesky of gs_chol.hip: M = L L^T, W = L^{-1}, and
 // G_uv = (W^T W)_uv = sum_{k >= max(u,v)} W_ku W_kv read from U = W^T, one wave per
 // CSR entry.  GSPARSE_XER_METHOD=ns takes gs_xer_ns.hip's Newton-Schulz instead.
-// This unit: the GSPARSE_XER_* knobs, the checks, the grounding, the read-out.
+// This unit: the GSPARSE_XER_* knobs, the checks, the grounding, the read-out.  Above
+// kXerDenseMax nodes, and through gs_exact_er_sparse at any size, G's columns come from
+// gs_xer_sparse.hip's batched CG instead and no dense matrix exists.
 #include <cstdlib>
 #include <cstring>
 
@@ -32,6 +34,7 @@ XerKnobs xer_knobs() {
     if ((e = getenv("GSPARSE_XER_TILE"))) k.tile = atoi(e) == 128 ? 128 : 64;
     k.full = getenv("GSPARSE_XER_FULL") != nullptr;
     k.debug = getenv("GSPARSE_XER_DEBUG") != nullptr;
+    if ((e = getenv("GSPARSE_XER_BATCH"))) k.batch = atoi(e) > 0 ? atoi(e) : 0;
     return k;
 }
 
@@ -162,6 +165,41 @@ static int32_t cholesky_scores(gs_ctx *c, const XerKnobs &kn, int64_t N, const u
 
 using namespace gs;
 
+static constexpr int64_t kXerDenseMax = 32768;  // the dense form's limit
+static constexpr double kXerCgRtol = 1e-12;     // the sparse form's defaults
+static constexpr int32_t kXerCgMaxIter = 5000;
+
+// the sparse form behind both entry points: checks and grounding as the dense form's
+static void exact_er_sparse(gs_ctx *c, double *out, int loc, double cg_rtol, int32_t cg_max_iter,
+                            int32_t *batches, int64_t *cg_iterations) {
+    Graph &g = c->g;
+    GS_CHECK(cg_rtol > 0.0 && cg_rtol < 1.0, GS_EINVAL, "cg_rtol in (0, 1)");
+    GS_CHECK(cg_max_iter >= 1, GS_EINVAL, "cg_max_iter >= 1");
+    GS_HIP(hipSetDevice(c->device));
+    const XerKnobs kn = xer_knobs();
+    const int64_t nnz = g.nnz;
+    if (batches) *batches = 0;
+    if (cg_iterations) *cg_iterations = 0;
+    double *dout = (double *)out_device(c, c->outbuf, out, sizeof(double) * (nnz ? nnz : 1), loc);
+    if (g.n > 0) {
+        check_symmetric_weights(c);
+        const uint8_t *flag = ground_components(c, g.n);
+        xer_sparse_scores(c, kn, flag, cg_rtol, cg_max_iter, dout, batches, cg_iterations);
+    }
+    finish_out(c, out, dout, sizeof(double) * nnz, loc);
+}
+
+extern "C" int gs_exact_er_sparse(gs_ctx *c, double *out, int loc, double cg_rtol,
+                                  int32_t cg_max_iter, int32_t *batches, int64_t *cg_iterations) {
+    return guard([&] {
+        GS_CHECK(c, GS_EINVAL, "null context");
+        ensure_transpose(c);
+        GS_CHECK(c->g.symmetric, GS_EUNSUPPORTED,
+                 "exact effective resistance needs a symmetric adjacency (metrics.py:138)");
+        exact_er_sparse(c, out, loc, cg_rtol, cg_max_iter, batches, cg_iterations);
+    });
+}
+
 extern "C" int gs_exact_er(gs_ctx *c, double *out, int loc, int32_t *iterations) {
     return guard([&] {
         GS_CHECK(c, GS_EINVAL, "null context");
@@ -169,8 +207,10 @@ extern "C" int gs_exact_er(gs_ctx *c, double *out, int loc, int32_t *iterations)
         ensure_transpose(c);
         GS_CHECK(g.symmetric, GS_EUNSUPPORTED,
                  "exact effective resistance needs a symmetric adjacency (metrics.py:138)");
-        GS_CHECK(g.n <= 32768, GS_EUNSUPPORTED, "exact effective resistance is dense O(n^3): n=%lld",
-                 (long long)g.n);
+        if (g.n > kXerDenseMax) {
+            exact_er_sparse(c, out, loc, kXerCgRtol, kXerCgMaxIter, iterations, nullptr);
+            return;
+        }
         GS_HIP(hipSetDevice(c->device));
         const XerKnobs kn = xer_knobs();
         const int64_t nnz = g.nnz, N = dense_pad(g.n);

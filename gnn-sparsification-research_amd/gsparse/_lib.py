@@ -108,6 +108,9 @@ SIGNATURES = {
     "gs_jsel_mask": (_int, [_vp, _int, _vp, _i64, _int, _vp, _int]),
     "gs_bb_class_counts": (_int, [_vp, _vp, _int, _vp, _i64, _int, ctypes.POINTER(_i64)]),
     "gs_exact_er": (_int, [_vp, _vp, _int, ctypes.POINTER(_i32)]),
+    "gs_exact_er_sparse": (_int, [_vp, _vp, _int, _f64, _i32, ctypes.POINTER(_i32),
+                                  ctypes.POINTER(_i64)]),
+    "gs_xer_sparse_plan": (_int, [_i64, _i32, _vp]),
     "gs_pair_distances": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _int, _i64, _vp, _vp,
                                  _vp]),
     "gs_common_neighbors": (_int, [_vp, _vp, _int]),

@@ -155,7 +155,12 @@ class GraphSparsifier:
 
     # --------------------------------------------------------------- scores
     def compute_scores(self, metric: str) -> np.ndarray:
-        """Compute or retrieve cached edge scores (core.py:140-191), CSR order."""
+        """Compute or retrieve cached edge scores (core.py:140-191), CSR order.
+
+        "effective_resistance" has no size limit: up to 32768 nodes the grounded inverse is
+        dense (fp64-MFMA Cholesky), above its columns come from the batched sparse CG
+        (Engine.exact_er), which raises GsparseNotConverged rather than return a value
+        when a solve stops at its iteration cap."""
         metric_key = self._normalize_metric_name(metric)
         if metric_key in self._score_cache:
             return self._score_cache[metric_key]

@@ -117,6 +117,17 @@ def er_reg_layout_w(n: int, blas_threads: int, window: int, unit: bool = True) -
     return d
 
 
+def xer_sparse_plan(n: int, cus: int = 0) -> dict:
+    """The plan the sparse exact effective resistance (gs_exact_er_sparse) follows for an
+    n-node graph on a device of ``cus`` compute units (0: 256), under GSPARSE_XER_BATCH
+    as it is now (gs_xer_sparse_plan; host code, no device): batch, the columns solved
+    at a time (a multiple of 64); budget_bytes, what its four n x batch fp64 blocks may
+    take; chunks and chunk_rows, the row chunks of its reductions (functions of n alone)."""
+    o = np.zeros(4, dtype=np.int64)
+    _lib.check(_lib.lib().gs_xer_sparse_plan(int(n), int(cus), ptr(o)), "gs_xer_sparse_plan")
+    return dict(zip(("batch", "budget_bytes", "chunks", "chunk_rows"), o.tolist()))
+
+
 def bb_geometry(n: int, nsrc: int, nranks: int = 1, lpart: int = 0) -> dict:
     """The numbers a metric backbone run of n nodes (E > 0) takes on rank lpart of nranks,
     under the GSPARSE_BB_* variables as they are now (gs_bb_geometry; host code, no
@@ -474,15 +485,41 @@ class Engine:
         return v.value
 
     # -- selection ------------------------------------------------------------
-    def exact_er(self, out=None):
-        """calculate_effective_resistance_scores (metrics.py:124-175) -- gs_exact_er:
-        the grounded Laplacian's inverse by a blocked fp64-MFMA Cholesky
-        (GSPARSE_XER_METHOD=ns: Newton-Schulz).  exact_er_iterations: 64-row blocks,
-        or the last Newton-Schulz step."""
+    def exact_er(self, out=None, method: str = "auto", cg_rtol: float = 1e-12,
+                 cg_max_iter: int = 5000):
+        """calculate_effective_resistance_scores (metrics.py:124-175), one score per CSR
+        entry from the grounded Laplacian's inverse.
+
+        method "auto": gs_exact_er (up to 32768 nodes the dense form, a blocked fp64-MFMA
+        Cholesky, GSPARSE_XER_METHOD=ns: Newton-Schulz; above, the sparse form with its
+        default tolerances); "dense": gs_exact_er on a graph the dense form takes
+        (NotImplementedError above 32768 nodes); "sparse": gs_exact_er_sparse at any size,
+        the inverse's columns by a Jacobi-preconditioned CG, a batch of columns at a time
+        (GSPARSE_XER_BATCH overrides the batch width), each column to relative residual
+        cg_rtol within cg_max_iter iterations.  exact_er_iterations: 64-row blocks, the last
+        Newton-Schulz step, or the sparse form's batches; exact_er_cg_iterations: the
+        columns' CG iterations summed, of a method="sparse" call (None otherwise: gs_exact_er
+        reports the batches only).  A batch that stops
+        at the cap with a column open raises GsparseNotConverged (a RuntimeError): ``out`` is
+        left as it was, the counts are recorded."""
+        if method not in ("auto", "dense", "sparse"):
+            raise ValueError(f"method must be 'auto', 'dense' or 'sparse', got {method!r}")
+        self.exact_er_iterations = self.exact_er_cg_iterations = None
+        if method == "dense" and self.n > 32768:
+            raise NotImplementedError(f"the dense exact effective resistance is O(n^3): n={self.n}")
         o, loc = self._out(0, self.nnz, out)
-        it = ctypes.c_int32(0)
-        self.ctx.call("gs_exact_er", ptr(o), loc, ctypes.byref(it))
-        self.exact_er_iterations = it.value
+        it, cg = ctypes.c_int32(0), ctypes.c_int64(0)
+        sparse = method == "sparse"
+        try:
+            if sparse:
+                self.ctx.call("gs_exact_er_sparse", ptr(o), loc, float(cg_rtol), int(cg_max_iter),
+                              ctypes.byref(it), ctypes.byref(cg))
+            else:
+                self.ctx.call("gs_exact_er", ptr(o), loc, ctypes.byref(it))
+        finally:
+            self.exact_er_iterations = it.value
+            if sparse:
+                self.exact_er_cg_iterations = cg.value
         return o
 
     def segment_argmax(self, scores: np.ndarray, src: np.ndarray, num_nodes: int) -> np.ndarray:

@@ -92,14 +92,19 @@ def calculate_adamic_adar_scores(adj: sp.csr_matrix) -> NDArray[np.float64]:
 
 
 def calculate_effective_resistance_scores(adj: sp.csr_matrix) -> NDArray[np.float64]:
-    """EXACT effective resistance (metrics.py:124-175), dense, on the MI355X.
+    """EXACT effective resistance (metrics.py:124-175) on the MI355X.
 
     The reference reads R(u,v) = P_uu + P_vv - 2 P_uv off pinv(L + 1e-10 I); this
     reads it off the inverse of L grounded at one node per component (equal in
-    exact arithmetic for every edge, whose endpoints share a component), by a
-    blocked Cholesky on fp64 MFMA (gs_exact_er).  Agrees with the reference to its own pinv rounding
+    exact arithmetic for every edge, whose endpoints share a component).  Up to
+    32768 nodes the inverse is dense, by a blocked Cholesky on fp64 MFMA
+    (gs_exact_er); above, its columns come from a Jacobi-preconditioned CG batched
+    over the columns (gs_exact_er_sparse, relative residual 1e-12, at most 5000
+    iterations per column), no dense matrix exists, and a graph whose solves do not
+    converge within the cap (long chains) raises GsparseNotConverged instead of
+    returning a value.  Agrees with the reference to its own pinv rounding
     noise (<= 1e-4 relative on the fixtures; DESIGN.md §Exact ER).  Symmetric
-    adjacency with n <= 32768 only (NotImplementedError otherwise)."""
+    adjacency only (NotImplementedError otherwise)."""
     eng, perm = _engine(adj)
     return _unpermute(eng.exact_er(), perm)
 

@@ -456,10 +456,35 @@ int gs_pair_distances(gs_ctx *ctx, int64_t n, int64_t E, const int64_t *src, con
  * inverse of the grounded Laplacian M (one ground node per connected
  * component, its row/column read as zero), G from a blocked fp64-MFMA Cholesky
  * M = L L^T and L^-1 (GSPARSE_XER_METHOD=ns: Newton-Schulz); max(., 1e-10) as
- * the reference clamps.  Dense: n <= 32768 (GS_EUNSUPPORTED above, and for a
- * directed adjacency).  *iterations (may be NULL) receives the number of 64-row
- * blocks (Cholesky) or Newton-Schulz steps. */
+ * the reference clamps.  n <= 32768: the dense form; *iterations (may be NULL)
+ * receives the number of 64-row blocks (Cholesky) or Newton-Schulz steps.
+ * Above: gs_exact_er_sparse with cg_rtol = 1e-12 and cg_max_iter = 5000, and
+ * *iterations receives its batch count.  GS_EUNSUPPORTED for a directed
+ * adjacency or asymmetric weights. */
 int gs_exact_er(gs_ctx *ctx, double *out, int out_loc, int32_t *iterations);
+/* The same scores with no dense matrix, for a symmetric graph of any n: for
+ * every node u that is not grounded the column g_u of G solves M g_u = e_u by
+ * CG on the ungrounded rows, Jacobi-preconditioned (the weighted degrees;
+ * stored diagonal entries are no part of L), to a relative residual cg_rtol
+ * within cg_max_iter iterations.  The columns run B at a time (B a multiple of
+ * 64 from n and the device, GSPARSE_XER_BATCH overrides; four n x B fp64 blocks
+ * and O(n + nnz) of memory), each with its own recurrence and stopping test; a
+ * converged batch leaves G_uu and, per CSR entry (u,v) with u < v, G_vu, and
+ * entry (v,u) takes the score of (u,v): out[e] == out[tpos[e]] bit for bit.
+ * Reductions are two-stage in a fixed order that depends on n alone: two calls,
+ * and two batch widths, give the same bits.  GS_EINVAL for cg_rtol outside
+ * (0, 1) or cg_max_iter < 1, GS_EUNSUPPORTED for a directed adjacency or
+ * asymmetric weights, GS_ENOCONV when a batch stops at cg_max_iter with a
+ * column still open: out is then left untouched.  *batches (converged batches)
+ * and *cg_iterations (the columns' iterations, summed) are written in both
+ * cases; each may be NULL. */
+int gs_exact_er_sparse(gs_ctx *ctx, double *out, int out_loc, double cg_rtol,
+                       int32_t cg_max_iter, int32_t *batches, int64_t *cg_iterations);
+/* The sparse form's plan for an n-node graph on a device of cus compute units
+ * (<= 0: 256), under GSPARSE_XER_BATCH as it is now (host code, no device):
+ * out = B, the byte budget of the four blocks, the row chunks of its vector
+ * passes and the rows per chunk (both functions of n alone). */
+int gs_xer_sparse_plan(int64_t n, int32_t cus, int64_t out[4]);
 
 /* ---- compute_topology_metrics (metrics.py:445-520) on the resident graph ----
  * The resident graph must be symmetric; the clustering and the counts expect
