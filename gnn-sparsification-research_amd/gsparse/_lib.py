@@ -85,6 +85,9 @@ SIGNATURES = {
     "gs_random_mask": (_int, [_vp, _vp, _int, _i64, _i64, _vp, _int, _i64, _vp, _int,
                               ctypes.POINTER(_f64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                               ctypes.POINTER(_i64)]),
+    "gs_spanning_forest": (_int, [_vp, _vp, _int, _i64, _vp, _vp, _int, _i64, _i64, _int, _int, _vp,
+                                  _int, _vp, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                  ctypes.POINTER(_i32)]),
     "gs_metric_backbone": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _int, _f64, _vp, _int,
                                   ctypes.POINTER(_i64)]),
     "gs_metric_backbone_part": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _int, _f64, _int,

@@ -29,7 +29,8 @@ from ._lib import Context
 from .data import Data
 from .engine import Engine
 from .metric_backbone import compute_metric_backbone
-from .selection import degree_aware_mask_device, numpy_topk_mask, sampled_mask_device
+from .selection import (connected_mask_device, degree_aware_mask_device, numpy_topk_mask,
+                        sampled_mask_device)
 
 
 def _device_index(device) -> int | None:
@@ -282,6 +283,39 @@ class GraphSparsifier:
         mask = degree_aware_mask_device(self._engine, scores, self.data.edge_index.cpu().numpy(),
                                         self.num_nodes, self.num_edges, retention_ratio,
                                         min_edges_per_node, info=self.last_selection)
+        sparse_edge_index = self.data.edge_index[:, torch.from_numpy(mask).to(
+            self.data.edge_index.device)].to(self.device)
+        sparse_data = self.data.clone()
+        sparse_data.edge_index = sparse_edge_index
+        if return_mask:
+            return sparse_data, torch.from_numpy(mask)
+        return sparse_data
+
+    def sparsify_connected(self, metric: str, retention_ratio: float, return_mask: bool = False,
+                           keep_lowest: bool = False):
+        """Top-k with a retention budget that cannot change the component structure: the
+        maximum spanning forest under the scores is kept first, in both directions, and
+        the rest of ``int(E*r)`` is spent on the best other columns (not in the
+        reference).  The order is the stable one -- (score, index), a strict total order
+        -- so the result is unique and ``tie_break`` is not consulted.  When the forest
+        alone is over the budget it is kept whole (as ``sparsify_degree_aware`` keeps its
+        guarantees).  One score per ``edge_index`` column is needed: ValueError when the
+        canonical CSR merged duplicate columns.
+
+        ``last_selection`` records ``path``, ``forest`` (columns of the forest),
+        ``guaranteed`` (with reverse directions and duplicates), ``rounds``,
+        ``over_budget`` and the fill's ``cut`` / ``beyond`` / ``tied``."""
+        if not 0 < retention_ratio <= 1:
+            raise ValueError(f"retention_ratio must be in (0, 1], got {retention_ratio}")
+        if retention_ratio == 1.0:
+            if return_mask:
+                return self.data.clone(), torch.ones(self.num_edges, dtype=torch.bool)
+            return self.data.clone()
+        scores = self.compute_scores(metric)
+        self.last_selection = {}
+        mask = connected_mask_device(self._engine, scores, self.data.edge_index.cpu().numpy(),
+                                     self.num_nodes, self.num_edges, retention_ratio, keep_lowest,
+                                     info=self.last_selection)
         sparse_edge_index = self.data.edge_index[:, torch.from_numpy(mask).to(
             self.data.edge_index.device)].to(self.device)
         sparse_data = self.data.clone()

@@ -691,6 +691,55 @@ class Engine:
             raise IndexError(f"{bad.value} index entries are out of bounds for axis 0 with size {m}")
         return (mask[:E].view(bool) if out is None else out), cut.value, nb.value, nt.value
 
+    # -- maximum spanning forest (gs_spanning_forest) ---------------------------
+    def spanning_forest(self, scores, src, dst, num_nodes: int, keep_lowest: bool = False,
+                        expand: bool = False, out=None):
+        """gs_spanning_forest: the forest ``F`` Kruskal's walk adds over the columns of
+        ``(src, dst)``, best first in the strict total order ``(key(score), index)`` --
+        gs_topk_mask's keys and stable tie rule; ``keep_lowest`` reverses it.  With
+        ``expand`` the mask holds every column whose unordered pair is a forest column's
+        (the reverse direction, duplicates).  ``scores`` (float64, one per column) and
+        ``src`` / ``dst`` (int64): numpy arrays or CUDA tensors; ``out``: an optional CUDA
+        uint8/bool tensor of >= E elements that receives the mask on the device.
+
+        Returns ``(mask, labels, info)``: ``labels`` (int32, one representative node per
+        component; a CUDA tensor when the ids are) and ``info`` with ``n_forest``
+        (``|F|`` = num_nodes - components), ``n_marked`` (mask bytes set) and ``rounds``.
+        ValueError for fewer scores than columns or an id outside ``[0, num_nodes)``."""
+        if isinstance(scores, np.ndarray):
+            scores, sloc = np.ascontiguousarray(scores, dtype=np.float64), GS_HOST
+        elif scores.is_cuda:
+            scores, sloc = scores.contiguous(), GS_DEVICE
+        else:
+            scores, sloc = np.ascontiguousarray(scores.numpy(), dtype=np.float64), GS_HOST
+        if str(scores.dtype) not in ("float64", "torch.float64"):
+            raise TypeError(f"scores must be float64, got {scores.dtype}")
+        src, loc = self._i64_input(src)
+        dst, dloc = self._i64_input(dst)
+        if loc != dloc:
+            raise ValueError("src and dst must both be numpy arrays or both CUDA tensors")
+        E, n = int(src.shape[0]), int(num_nodes)
+        if int(dst.shape[0]) != E:
+            raise ValueError(f"src holds {E} ids, dst {int(dst.shape[0])}")
+        if out is None:
+            mask, mloc = np.zeros(max(E, 1), dtype=np.uint8), GS_HOST
+        else:
+            if not out.is_cuda or out.numel() < E or out.element_size() != 1:
+                raise ValueError("out must be a CUDA uint8/bool tensor of >= E elements")
+            mask, mloc = out, GS_DEVICE
+        if loc == GS_DEVICE:
+            import torch
+
+            labels = torch.empty(max(n, 1), dtype=torch.int32, device=src.device)
+        else:
+            labels = np.empty(max(n, 1), dtype=np.int32)
+        nf, nm, rounds = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        self.ctx.call("gs_spanning_forest", ptr(scores), sloc, int(scores.shape[0]), ptr(src), ptr(dst),
+                      loc, E, n, int(bool(keep_lowest)), int(bool(expand)), ptr(mask), mloc,
+                      ptr(labels), loc, ctypes.byref(nf), ctypes.byref(nm), ctypes.byref(rounds))
+        info = {"n_forest": nf.value, "n_marked": nm.value, "rounds": rounds.value}
+        return (mask[:E].view(bool) if out is None else out), labels[:max(n, 0)], info
+
     def sample_probs(self, scores: np.ndarray):
         """gs_sample_probs: (probs, total) of sparsify_sampled's normalisation."""
         scores = np.ascontiguousarray(scores, dtype=np.float64)

@@ -7,6 +7,11 @@ own calls on the host; the ``*_device`` forms run the
 same selection on the MI355X and give the same result, with the reference's
 call only where NumPy's own behaviour decides.  The plain functions take
 arrays so they are testable without a GPU.
+
+``connected_mask`` is the one selection here that is not the reference's: a
+top-k that cannot change the component structure (the maximum spanning forest
+under the scores is kept first).  Its order is the stable one, a strict total
+order, so its result is unique and NumPy's unstable argsort is never consulted.
 """
 
 from __future__ import annotations
@@ -197,6 +202,109 @@ def degree_aware_mask_device(engine, scores: np.ndarray, edge_index: np.ndarray,
         mask[cand[:k2]] = True
         return mask
     return mask | sel
+
+
+def spanning_forest_host(scores: np.ndarray, src: np.ndarray, dst: np.ndarray, num_nodes: int,
+                         keep_lowest: bool = False):
+    """The forest of gs_spanning_forest on the host: Kruskal's walk with a union-find over
+    the columns, best first.  Ascending order is ``np.lexsort((arange(E), scores))`` --
+    (score, index) with -0.0 == +0.0 and NaN last; the walk runs it backwards, or
+    forwards with ``keep_lowest``.  Returns ``(forest, parent)``: the bool mask of the
+    columns that joined two components, and the union-find's parents."""
+    E = len(src)
+    if len(scores) < E:
+        raise ValueError(f"{len(scores)} scores for {E} columns: one score per edge_index column "
+                         "is needed")
+    order = np.lexsort((np.arange(E), np.asarray(scores, dtype=np.float64)[:E]))
+    if not keep_lowest:
+        order = order[::-1]
+    parent = list(range(num_nodes))
+    forest = np.zeros(E, dtype=bool)
+    us, vs = np.asarray(src)[order].tolist(), np.asarray(dst)[order].tolist()
+    left = num_nodes - 1
+    for col, u, v in zip(order.tolist(), us, vs):
+        while parent[u] != u:
+            parent[u] = parent[parent[u]]
+            u = parent[u]
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        if u != v:
+            parent[u] = v
+            forest[col] = True
+            left -= 1
+            if not left:
+                break
+    return forest, np.asarray(parent, dtype=np.int64)
+
+
+def guaranteed_columns(forest: np.ndarray, src: np.ndarray, dst: np.ndarray,
+                       num_nodes: int) -> np.ndarray:
+    """Every column whose unordered pair {src, dst} is the pair of a forest column."""
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    keys = np.minimum(src, dst) * (num_nodes + 1) + np.maximum(src, dst)
+    return np.isin(keys, keys[forest])
+
+
+def connected_mask(scores: np.ndarray, edge_index: np.ndarray, num_nodes: int, num_edges: int,
+                   retention_ratio: float, keep_lowest: bool = False) -> np.ndarray:
+    """Connectivity-preserving top-k: the maximum spanning forest under the scores, in
+    both directions (and every duplicate of its pairs), then the best of the other
+    columns until ``int(E * r)`` are kept.  The kept columns have the component
+    partition of the whole graph; when the guaranteed set alone is over the budget it
+    is the mask (the precedent of ``degree_aware_mask``).
+
+    Column i is better than column j when ``(score, index)`` is larger (``keep_lowest``:
+    smaller), -0.0 == +0.0, NaN the largest: the stable top-k's order, strict and
+    total, so the result is unique."""
+    ei = np.asarray(edge_index)
+    src, dst = ei[0][:num_edges], ei[1][:num_edges]
+    scores = np.asarray(scores, dtype=np.float64)
+    forest, _ = spanning_forest_host(scores, src, dst, num_nodes, keep_lowest)
+    mask = guaranteed_columns(forest, src, dst, num_nodes)
+    num_keep = int(num_edges * retention_ratio)
+    have = int(mask.sum())
+    if have < num_keep:
+        order = np.lexsort((np.arange(num_edges), scores[:num_edges]))
+        if not keep_lowest:
+            order = order[::-1]
+        cand = order[~mask[order]]
+        mask[cand[: num_keep - have]] = True
+    return mask
+
+
+def connected_mask_device(engine, scores: np.ndarray, edge_index: np.ndarray, num_nodes: int,
+                          num_edges: int, retention_ratio: float, keep_lowest: bool = False,
+                          info: dict | None = None) -> np.ndarray:
+    """connected_mask on the MI355X; the same mask.  The guaranteed set is
+    gs_spanning_forest's expanded forest (Boruvka rounds over the columns); the fill is
+    gs_topk_mask's stable select over the scores of the other columns alone, in column
+    order -- the guaranteed columns are taken out, not given a sentinel score, so
+    +-inf and NaN scores cannot bring one back or push one out.
+
+    ``info`` (optional dict) receives ``path`` ("device"), ``forest`` (``|F|``),
+    ``guaranteed`` (``|G|``), ``rounds``, ``over_budget`` and, when columns were
+    filled, the fill's ``cut`` / ``beyond`` / ``tied``."""
+    if info is None:
+        info = {}
+    ei = np.asarray(edge_index)
+    src = np.ascontiguousarray(ei[0][:num_edges], dtype=np.int64)
+    dst = np.ascontiguousarray(ei[1][:num_edges], dtype=np.int64)
+    scores = np.ascontiguousarray(scores, dtype=np.float64)
+    mask, _, f = engine.spanning_forest(scores, src, dst, num_nodes, keep_lowest, expand=True)
+    num_keep = int(num_edges * retention_ratio)
+    have = int(f["n_marked"])
+    info.update(path="device", forest=f["n_forest"], guaranteed=have, rounds=f["rounds"],
+                over_budget=have > num_keep, cut=float("nan"), beyond=0, tied=0)
+    mask = mask.copy()
+    if have >= num_keep:
+        return mask
+    rest = np.nonzero(~mask)[0]
+    sel, cut, beyond, tied = engine.topk_mask(scores[:num_edges][rest], len(rest), num_keep - have,
+                                              keep_lowest)
+    info.update(cut=cut, beyond=beyond, tied=tied)
+    mask[rest[sel]] = True
+    return mask
 
 
 def numpy_topk_mask(scores: np.ndarray, num_edges: int, num_keep: int,

@@ -358,6 +358,27 @@ int gs_random_mask(gs_ctx *ctx, const double *scores, int s_loc, int64_t m, int6
                    const int64_t *inverse, int i_loc, int64_t E, uint8_t *mask, int m_loc,
                    double *cut, int64_t *n_beyond, int64_t *n_tied, int64_t *n_bad);
 
+/* ---- maximum spanning forest under per-column scores ------------------------
+ * The columns are the E columns of (src, dst), scores[i] belongs to column i
+ * (nscores >= E).  Column i is better than column j when (key(score), index) is
+ * lexicographically larger -- keep_lowest: smaller -- with gs_topk_mask's keys
+ * (-0.0 == +0.0, NaN the largest) and its stable tie rule: a strict total order.
+ * F = the columns Kruskal's walk, best first, adds because they join two components
+ * of the undirected graph on n nodes; self-loop columns never do.  F is unique and
+ * |F| = n - c, c = the components of that graph (isolated nodes count).
+ * expand == 0: mask[i] = 1 on F.  expand != 0: mask[i] = 1 on every column whose
+ * unordered pair {src, dst} is the pair of a column of F (the reverse direction
+ * and duplicates), through gs_undirected_ids.
+ * labels (optional, int32[n] at l_loc): one representative node per component.
+ * *n_forest = |F|, *n_marked = mask bytes set, *rounds = Boruvka rounds that added a
+ * column (<= ceil(log2 n)).  The host waits once per round.  E == 0: an empty mask.
+ * GS_EINVAL: an id outside [0, n), nscores < E, n < 1.  GS_EUNSUPPORTED: n >= 2^31.
+ * The result is the same bytes on every run. */
+int gs_spanning_forest(gs_ctx *ctx, const double *scores, int s_loc, int64_t nscores,
+                       const int64_t *src, const int64_t *dst, int e_loc, int64_t E, int64_t n,
+                       int keep_lowest, int expand, uint8_t *mask, int m_loc, int32_t *labels,
+                       int l_loc, int64_t *n_forest, int64_t *n_marked, int32_t *rounds);
+
 int gs_metric_backbone(gs_ctx *ctx, int64_t n, int64_t E, const int64_t *src,
                        const int64_t *dst, const double *w, int64_t nw, int loc, double eps,
                        uint8_t *keep, int keep_loc, int64_t *n_relax);
