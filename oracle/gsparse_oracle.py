@@ -251,13 +251,14 @@ def laplacian_reg(indptr, indices, data, n, reg=1e-6):
     return L_reg
 
 
-def approx_er_projection(indptr, indices, n, epsilon=0.3, seed=42):
-    """metrics.py:232-275: edges u<v in CSR order, k, R = N(0,1)^{m x k}/sqrt(k), Y = B @ R."""
+def approx_er_projection(indptr, indices, n, epsilon=0.3, seed=42, k=None):
+    """metrics.py:232-275: edges u<v in CSR order, k, R = N(0,1)^{m x k}/sqrt(k), Y = B @ R.
+    k given: that many JL columns instead of metrics.py:248's (the stream tests choose m * k)."""
     rows = csr_rows(indptr)
     mask = rows < indices
     u_e, v_e = rows[mask], indices[mask].astype(np.int64)
     m = len(u_e)
-    k = jl_dim(n, epsilon)
+    k = jl_dim(n, epsilon) if k is None else int(k)
     rng = np.random.default_rng(seed)
     B = sp.csr_matrix((np.concatenate([np.ones(m), -np.ones(m)]),
                        (np.concatenate([u_e, v_e]), np.concatenate([np.arange(m), np.arange(m)]))),
