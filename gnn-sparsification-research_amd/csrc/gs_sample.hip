@@ -18,23 +18,14 @@
 //                  per round.  A draw never lands on a zeroed index (the cdf is flat there
 //                  and the search is side='right'), so the order of a round's claims does
 //                  not matter and the atomics leave the result deterministic.
-#include "gs_internal.hpp"
-#include "gs_sample.hpp"
+#include "gs_sample_dev.hpp"
 
 namespace gs {
 
 static constexpr int kTile = GS_SAMPLE_TILE;
 static_assert(kTile % 128 == 0, "the cumsum's staging waves take 128 and 64 elements per step");
 static constexpr int64_t kSub = GS_SAMPLE_SUBTREE;
-static constexpr int kRun = 8;  // consecutive draws per thread (one pcg_advance each)
-
-struct SmpState {
-    double total;              // p.sum()
-    double last;               // cumsum(p)[-1] of the round
-    unsigned long long count;  // indices claimed so far
-    int bad;                   // the degenerate gate
-    int pad;
-};
+static constexpr int kRun = kSampleRun;
 
 __global__ void k_smp_prep(const double *__restrict__ s, int64_t n, double *__restrict__ p) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
@@ -216,10 +207,9 @@ __global__ void __launch_bounds__(256) k_smp_doubles(u128 s0, u128 inc, int64_t 
     for (int64_t j = j0; j < j1; ++j) out[j] = sample_double(g.next());
 }
 
-static unsigned run_grid(int64_t n) { return (unsigned)((n + 256 * (int64_t)kRun - 1) / (256 * (int64_t)kRun)); }
+static unsigned run_grid(int64_t n) { return sample_run_grid(n); }
 
-// p = max(nan_to_num(s), 1e-8) / total into p[n]; st->total, st->bad set
-static void sample_probs(gs_ctx *c, const double *ds, int64_t n, double *p, SmpState *st) {
+void sample_total_device(gs_ctx *c, const double *p, int64_t n, SmpState *st, SmpState *host) {
     hipStream_t s = c->stream;
     std::vector<int64_t> offs;
     sample_total(n, kSub, [&](int64_t off, int64_t) {
@@ -230,25 +220,38 @@ static void sample_probs(gs_ctx *c, const double *ds, int64_t n, double *p, SmpS
     offs.push_back(n);
     int64_t *doffs = (int64_t *)c->buf("smp_offs").ensure(sizeof(int64_t) * offs.size());
     double *part = (double *)c->buf("smp_part").ensure(sizeof(double) * ntask);
-    hipEvent_t t0 = prof_begin(c);
     GS_HIP(hipMemcpyAsync(doffs, offs.data(), sizeof(int64_t) * offs.size(), hipMemcpyHostToDevice, s));
-    k_smp_prep<<<grid_for(n, 256, 8192), 256, 0, s>>>(ds, n, p);
     k_smp_partial<<<grid_for(ntask, 64), 64, 0, s>>>(p, doffs, ntask, part);
     k_smp_total<<<1, 1, 0, s>>>(part, n, ntask, st);
-    k_smp_norm<<<grid_for(n, 256, 8192), 256, 0, s>>>(p, n, st);
     GS_HIP(hipGetLastError());
-    prof_end(c, t0, "sample_probs", 8.0 * 4 * (double)n);
+    if (host) GS_HIP(hipMemcpyAsync(host, st, sizeof(SmpState), hipMemcpyDeviceToHost, s));
     GS_HIP(hipStreamSynchronize(s));  // offs is a host temporary
 }
 
-static void cumsum_ordered(gs_ctx *c, const double *p, int64_t n, double *cdf, SmpState *st) {
+// p = max(nan_to_num(s), 1e-8) / total into p[n]; st->total, st->bad set
+static void sample_probs(gs_ctx *c, const double *ds, int64_t n, double *p, SmpState *st) {
+    hipStream_t s = c->stream;
+    hipEvent_t t0 = prof_begin(c);
+    k_smp_prep<<<grid_for(n, 256, 8192), 256, 0, s>>>(ds, n, p);
+    sample_total_device(c, p, n, st);
+    k_smp_norm<<<grid_for(n, 256, 8192), 256, 0, s>>>(p, n, st);
+    GS_HIP(hipGetLastError());
+    prof_end(c, t0, "sample_probs", 8.0 * 4 * (double)n);
+}
+
+void cumsum_ordered(gs_ctx *c, const double *p, int64_t n, double *cdf, SmpState *st) {
     hipEvent_t t0 = prof_begin(c);
     k_smp_cumsum<<<1, 256, 0, c->stream>>>(p, n, cdf, st);
     GS_HIP(hipGetLastError());
     prof_end(c, t0, "sample_cumsum", 8.0 * 2 * (double)n);
 }
 
-static u128 make_u128(uint64_t hi, uint64_t lo) { return ((u128)hi << 64) | lo; }
+void cdf_divide(gs_ctx *c, double *cdf, int64_t n, const SmpState *st) {
+    hipEvent_t t0 = prof_begin(c);
+    k_smp_div<<<grid_for(n, 256, 8192), 256, 0, c->stream>>>(cdf, n, st);
+    GS_HIP(hipGetLastError());
+    prof_end(c, t0, "sample_divide", 8.0 * 2 * (double)n);
+}
 
 }  // namespace gs
 
@@ -287,10 +290,8 @@ extern "C" int gs_sample_mask(gs_ctx *c, const double *scores, int s_loc, int64_
         while (n_uniq < num_keep) {
             const int64_t nd = num_keep - n_uniq;
             cumsum_ordered(c, p, E, cdf, st);
+            cdf_divide(c, cdf, E, st);
             hipEvent_t t0 = prof_begin(c);
-            k_smp_div<<<grid_for(E, 256, 8192), 256, 0, s>>>(cdf, E, st);
-            prof_end(c, t0, "sample_divide", 8.0 * 2 * (double)E);
-            t0 = prof_begin(c);
             k_smp_draw<<<run_grid(nd), 256, 0, s>>>(cdf, E, state, inc, nd, bits, p, st);
             GS_HIP(hipGetLastError());
             prof_end(c, t0, "sample_draw", 8.0 * (double)nd);

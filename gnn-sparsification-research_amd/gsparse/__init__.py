@@ -21,6 +21,7 @@ from .metrics import (
     compute_topology_preservation,
 )
 from .random import RandomBaseline, precompute_random_scores, random_sparsify
+from .selection import spectral_sample
 
 __all__ = [
     "GraphSparsifier",
@@ -41,4 +42,5 @@ __all__ = [
     "precompute_random_scores",
     "random_sparsify",
     "RandomBaseline",
+    "spectral_sample",
 ]

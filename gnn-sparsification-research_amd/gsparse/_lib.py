@@ -88,6 +88,10 @@ SIGNATURES = {
     "gs_spanning_forest": (_int, [_vp, _vp, _int, _i64, _vp, _vp, _int, _i64, _i64, _int, _int, _vp,
                                   _int, _vp, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                   ctypes.POINTER(_i32)]),
+    "gs_spectral_sample": (_int, [_vp, _vp, _int, _i64, _vp, _vp, _int, _i64, _i64, _i64, _int,
+                                  _u64, _u64, _u64, _u64, _vp, _int, _vp, _int, _vp, _int, _vp, _int,
+                                  ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                  ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
     "gs_metric_backbone": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _int, _f64, _vp, _int,
                                   ctypes.POINTER(_i64)]),
     "gs_metric_backbone_part": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _int, _f64, _int,

@@ -29,8 +29,9 @@ from ._lib import Context
 from .data import Data
 from .engine import Engine
 from .metric_backbone import compute_metric_backbone
-from .selection import (connected_mask_device, degree_aware_mask_device, numpy_topk_mask,
-                        sampled_mask_device)
+from .selection import (SPECTRAL_METHODS, connected_mask_device, degree_aware_mask_device,
+                        numpy_topk_mask, sampled_mask_device, spectral_mask_device,
+                        spectral_num_samples)
 
 
 def _device_index(device) -> int | None:
@@ -322,6 +323,66 @@ class GraphSparsifier:
         sparse_data.edge_index = sparse_edge_index
         if return_mask:
             return sparse_data, torch.from_numpy(mask)
+        return sparse_data
+
+    def sparsify_spectral(self, metric: str = "approx_er", num_samples: int | None = None,
+                          retention_ratio: float | None = None, seed: int = 42,
+                          method: str = "multinomial", return_mask: bool = False):
+        """Spectral sparsification by effective-resistance sampling (Spielman-Srivastava;
+        not in the reference): ``q`` draws with replacement over the undirected pairs with
+        probability proportional to the pair's score, and every kept pair reweighted by
+        ``count / (q p)``, so the weighted subgraph's Laplacian is an unbiased estimate of
+        the whole graph's.  The ``(1 +- eps)`` guarantee holds for the two effective
+        resistance metrics ("approx_er", "effective_resistance"); any other metric is
+        accepted and gives an unbiased, reweighted sample without that guarantee.
+
+        Exactly one of ``num_samples`` (``q`` itself) and ``retention_ratio`` (in (0, 1]:
+        ``q = max(1, int(m * ratio))`` over the ``m`` undirected pairs) is given.
+        ``method``: "multinomial" (at most ``q`` pairs survive) or "independent" (every
+        pair kept on its own with probability ``min(1, q p)``, no cumsum: the form for
+        very large graphs).  ``selection.spectral_sample`` defines the result; it is
+        drawn on the device (gs_spectral_sample), bit for bit.  One score per
+        ``edge_index`` column is needed -- ValueError when the canonical CSR merged
+        duplicate columns -- and every non-loop pair must have exactly its two columns:
+        ValueError otherwise (the weighted graph would not be symmetric).
+
+        The returned ``Data`` has ``edge_index[:, mask]`` and ``edge_weight`` (float32) on
+        ``self.device``; with ``return_mask`` also ``(mask, weight)``, a bool and a float64
+        tensor of length E.  ``last_selection`` records ``path``, ``method``, ``m``,
+        ``num_samples``, ``kept_pairs``, ``max_count``, ``draws`` and ``n_irregular``."""
+        spectral_num_samples(num_samples, retention_ratio)
+        if method not in SPECTRAL_METHODS:
+            raise ValueError(f"method must be one of {SPECTRAL_METHODS}, got {method!r}")
+        scores = self.compute_scores(metric)
+        if len(scores) < self.num_edges:
+            raise ValueError(f"{len(scores)} scores for {self.num_edges} columns: the canonical CSR "
+                             "merged duplicate columns, one score per edge_index column is needed")
+        ei = self.data.edge_index
+        if ei.is_cuda and ei.device.index == self._ctx.device:
+            ids = ei.to(torch.int64)
+        else:
+            ids = ei.detach().cpu().numpy().astype(np.int64, copy=False)
+        if num_samples is None:
+            _, m, status = self._engine.undirected_ids(ids[0], ids[1], self.num_nodes)
+            if status != 0:  # outside the device contract: the reference's own lines
+                e = ei.detach().cpu().numpy().astype(np.int64, copy=False)
+                keys = np.minimum(e[0], e[1]) * (self.num_nodes + 1) + np.maximum(e[0], e[1])
+                m = len(np.unique(keys))
+            num_samples = spectral_num_samples(None, retention_ratio, m)
+        self.last_selection = {}
+        mask, weight, _, _ = spectral_mask_device(self._engine, scores, ids, self.num_nodes,
+                                                  num_samples, seed, method, info=self.last_selection)
+        if self.last_selection["n_irregular"] > 0:
+            raise ValueError(f"{self.last_selection['n_irregular']} undirected pairs do not have "
+                             "exactly two edge_index columns (one direction only, or duplicates): "
+                             "the weighted graph would not be symmetric")
+        if isinstance(mask, np.ndarray):
+            mask, weight = torch.from_numpy(mask), torch.from_numpy(weight)
+        sparse_data = self.data.clone()
+        sparse_data.edge_index = ei[:, mask.to(ei.device)].to(self.device)
+        sparse_data.edge_weight = weight[mask].to(torch.float32).to(self.device)
+        if return_mask:
+            return sparse_data, (mask.cpu(), weight.cpu())
         return sparse_data
 
     def get_retention_curve_data(self, metric: str, retention_rates: list[float]) -> list[Data]:

@@ -740,6 +740,63 @@ class Engine:
         info = {"n_forest": nf.value, "n_marked": nm.value, "rounds": rounds.value}
         return (mask[:E].view(bool) if out is None else out), labels[:max(n, 0)], info
 
+    # -- spectral sparsification by effective-resistance sampling ---------------
+    SPECTRAL_METHODS = {"multinomial": 0, "independent": 1}
+
+    def spectral_sample(self, scores, src, dst, num_nodes: int, num_samples: int,
+                        rng: np.random.Generator, method: str = "multinomial"):
+        """gs_spectral_sample: ``selection.spectral_sample`` drawn from ``rng``'s current
+        state on the device (the generator itself is not advanced).  ``scores`` (float64,
+        one per column) and ``src`` / ``dst`` (int64): numpy arrays or CUDA tensors; the
+        results live where the ids do.
+
+        Returns ``(mask, weight, counts, inverse, info)``: bool[E], float64[E], int64[m],
+        int64[E] and ``info`` with ``status``, ``m``, ``kept_pairs``, ``max_count``,
+        ``n_irregular`` and ``draws``.  ``status`` 1 = degenerate input, nothing was
+        written (the arrays are None) and the specification decides on the host."""
+        if method not in self.SPECTRAL_METHODS:
+            raise ValueError(f"method must be one of {tuple(self.SPECTRAL_METHODS)}, got {method!r}")
+        if isinstance(scores, np.ndarray):
+            scores, sloc = np.ascontiguousarray(scores, dtype=np.float64), GS_HOST
+        elif scores.is_cuda:
+            scores, sloc = scores.contiguous(), GS_DEVICE
+        else:
+            scores, sloc = np.ascontiguousarray(scores.numpy(), dtype=np.float64), GS_HOST
+        if str(scores.dtype) not in ("float64", "torch.float64"):
+            raise TypeError(f"scores must be float64, got {scores.dtype}")
+        src, loc = self._i64_input(src)
+        dst, dloc = self._i64_input(dst)
+        if loc != dloc:
+            raise ValueError("src and dst must both be numpy arrays or both CUDA tensors")
+        E = int(src.shape[0])
+        if int(dst.shape[0]) != E:
+            raise ValueError(f"src holds {E} ids, dst {int(dst.shape[0])}")
+        words = self._pcg64_words(rng)
+        if loc == GS_DEVICE:
+            import torch
+
+            new = lambda dt: torch.empty(max(E, 1), dtype=dt, device=src.device)  # noqa: E731
+            mask, weight = new(torch.uint8), new(torch.float64)
+            counts, inverse = new(torch.int64), new(torch.int64)
+        else:
+            mask, weight = np.zeros(max(E, 1), dtype=np.uint8), np.zeros(max(E, 1), dtype=np.float64)
+            counts, inverse = np.zeros(max(E, 1), dtype=np.int64), np.zeros(max(E, 1), dtype=np.int64)
+        m, kept, mx, irr, draws = (ctypes.c_int64(0) for _ in range(5))
+        status = ctypes.c_int32(1)
+        self.ctx.call("gs_spectral_sample", ptr(scores), sloc, int(scores.shape[0]), ptr(src), ptr(dst),
+                      loc, E, int(num_nodes), min(max(int(num_samples), 0), 1 << 31),
+                      self.SPECTRAL_METHODS[method], *words,
+                      ptr(mask), loc, ptr(weight), loc, ptr(counts), loc, ptr(inverse), loc,
+                      ctypes.byref(m), ctypes.byref(kept), ctypes.byref(mx), ctypes.byref(irr),
+                      ctypes.byref(draws), ctypes.byref(status))
+        info = {"status": status.value, "m": m.value, "kept_pairs": kept.value, "max_count": mx.value,
+                "n_irregular": irr.value, "draws": draws.value}
+        if status.value != 0:
+            return None, None, None, None, info
+        if loc == GS_DEVICE:
+            return mask[:E].view(torch.bool), weight[:E], counts[:m.value], inverse[:E], info
+        return mask[:E].view(bool), weight[:E], counts[:m.value], inverse[:E], info
+
     def sample_probs(self, scores: np.ndarray):
         """gs_sample_probs: (probs, total) of sparsify_sampled's normalisation."""
         scores = np.ascontiguousarray(scores, dtype=np.float64)

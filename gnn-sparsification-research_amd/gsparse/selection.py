@@ -307,6 +307,126 @@ def connected_mask_device(engine, scores: np.ndarray, edge_index: np.ndarray, nu
     return mask
 
 
+SPECTRAL_METHODS = ("multinomial", "independent")
+
+
+def spectral_sample(scores, edge_index, num_nodes, num_samples, seed=42, method="multinomial"):
+    """Spectral sparsification by effective-resistance sampling (Spielman-Srivastava): the
+    executable specification of gs_spectral_sample and its host form.
+
+    ``num_samples`` draws over the undirected pairs of ``edge_index`` with probability
+    proportional to the pair's score -- for a unit-weight graph scored by an effective
+    resistance, ``w_e R_e`` -- and a kept pair is given the weight ``count / (q p)``, so
+    the weighted subgraph's Laplacian is an unbiased estimate of the whole graph's.  A
+    pair takes the score of its lowest column (the two directions need not agree);
+    loops and scores that are NaN, infinite or <= 0 are never drawn.  ``method``:
+    "multinomial" is ``rng.choice(m, q, replace=True, p=p)`` written out (cumsum, divide,
+    a right-sided search of ``rng.random(q)``); "independent" keeps every pair on its
+    own with probability ``min(1, q p)`` and the weight ``1 / min(1, q p)`` (no cumsum;
+    the expected number of kept pairs is at most q).
+
+    Returns ``(mask[E], weight[E], counts[m], inverse[E])``: the kept columns, their
+    float64 weights (0 where dropped), the draws per pair and every column's pair id.
+    ValueError for fewer scores than columns, a total that is not finite and positive,
+    ``num_samples`` outside [1, 2^31) and an unknown method."""
+    if method not in SPECTRAL_METHODS:
+        raise ValueError(f"method must be one of {SPECTRAL_METHODS}, got {method!r}")
+    ei = np.asarray(edge_index)
+    src, dst = ei[0].astype(np.int64, copy=False), ei[1].astype(np.int64, copy=False)
+    E = len(src)
+    q = int(num_samples)
+    scores = np.asarray(scores, dtype=np.float64)
+    if len(scores) < E:
+        raise ValueError(f"{len(scores)} scores for {E} columns: one score per edge_index column "
+                         "is needed")
+    keys = np.minimum(src, dst) * (num_nodes + 1) + np.maximum(src, dst)
+    inv = np.unique(keys, return_inverse=True)[1]  # random.py:23-30
+    m = int(inv.max()) + 1
+    first = np.full(m, E)
+    np.minimum.at(first, inv, np.arange(E))  # a pair's lowest column
+    r = scores[first]
+    ok = np.isfinite(r) & (r > 0) & (src[first] != dst[first])  # loops, NaN, inf, <= 0: p = 0
+    r = np.where(ok, r, 0.0)
+    with np.errstate(all="ignore"):
+        total = np.sum(r)  # NumPy's blocked pairwise sum, as gs_sample_probs
+    if not (np.isfinite(total) and total > 0):
+        raise ValueError(f"the scores of the {m} undirected pairs sum to {total}: a finite "
+                         "positive total is needed")
+    if not 1 <= q < 2**31:
+        raise ValueError(f"num_samples must be in [1, 2^31), got {q}")
+    p = r / total
+    rng = np.random.default_rng(seed)
+    w = np.zeros(m)
+    if method == "multinomial":  # == rng.choice(m, size=q, replace=True, p=p)
+        cdf = np.cumsum(p)
+        cdf /= cdf[-1]
+        idx = cdf.searchsorted(rng.random(q), side="right")
+        cnt = np.bincount(idx, minlength=m)
+        k = cnt > 0
+        w[k] = cnt[k] / (q * p[k])  # fl(q*p) then one IEEE divide
+    else:  # every pair on its own, no cumsum
+        pk = np.minimum(1.0, q * p)
+        k = rng.random(m) < pk
+        cnt = k.astype(np.int64)
+        w[k] = 1.0 / pk[k]
+    return cnt[inv] > 0, w[inv], cnt, inv
+
+
+def spectral_num_samples(num_samples=None, retention_ratio=None, m=None):
+    """The draw count of ``sparsify_spectral``: ``num_samples`` itself, or
+    ``max(1, int(m * retention_ratio))`` over the ``m`` undirected pairs (None while ``m``
+    is not known yet).  ValueError unless exactly one of the two is given, and for a
+    ratio outside (0, 1]."""
+    if (num_samples is None) == (retention_ratio is None):
+        raise ValueError("give exactly one of num_samples and retention_ratio")
+    if num_samples is not None:
+        return int(num_samples)
+    if not 0 < retention_ratio <= 1:
+        raise ValueError(f"retention_ratio must be in (0, 1], got {retention_ratio}")
+    return None if m is None else max(1, int(m * retention_ratio))
+
+
+def spectral_mask_device(engine, scores, edge_index, num_nodes: int, num_samples: int,
+                         seed: int = 42, method: str = "multinomial", info: dict | None = None):
+    """spectral_sample on the MI355X (gs_spectral_sample): the same mask, weights, counts
+    and ids, bit for bit.  ``scores`` and ``edge_index`` are numpy arrays or CUDA tensors;
+    the results live where ``edge_index`` does.
+
+    Degenerate inputs (ids outside gs_undirected_ids' contract, fewer scores than
+    columns, a total that is not finite and positive, ``num_samples`` outside
+    [1, 2^31)) are reported by the device and handed to spectral_sample, so its
+    exception surfaces.
+
+    ``info`` (optional dict) receives ``path`` ("device" or "host"), ``method``, ``m``
+    (undirected pairs), ``num_samples``, ``kept_pairs``, ``max_count``, ``draws``
+    (doubles of the PCG64 stream consumed) and ``n_irregular`` (non-loop pairs that do
+    not have exactly two columns)."""
+    if info is None:
+        info = {}
+    if method not in SPECTRAL_METHODS:
+        raise ValueError(f"method must be one of {SPECTRAL_METHODS}, got {method!r}")
+    q = int(num_samples)
+    rng = np.random.default_rng(seed)
+    mask, weight, counts, inverse, st = engine.spectral_sample(
+        scores, edge_index[0], edge_index[1], num_nodes, q, rng, method)
+    if st["status"] != 0:
+        to_np = lambda a: a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()  # noqa: E731
+        ei = np.stack([to_np(edge_index[0]), to_np(edge_index[1])])
+        mask, weight, counts, inverse = spectral_sample(to_np(scores), ei, num_nodes, q, seed, method)
+        src, dst = ei
+        ncol = np.bincount(inverse, minlength=len(counts))
+        first = np.full(len(counts), len(src))
+        np.minimum.at(first, inverse, np.arange(len(src)))
+        info.update(path="host", method=method, m=len(counts), num_samples=q,
+                    kept_pairs=int((counts > 0).sum()), max_count=int(counts.max()),
+                    draws=q if method == "multinomial" else len(counts),
+                    n_irregular=int(((ncol != 2) & (src[first] != dst[first])).sum()))
+        return mask, weight, counts, inverse
+    info.update(path="device", method=method, m=st["m"], num_samples=q, kept_pairs=st["kept_pairs"],
+                max_count=st["max_count"], draws=st["draws"], n_irregular=st["n_irregular"])
+    return mask, weight, counts, inverse
+
+
 def numpy_topk_mask(scores: np.ndarray, num_edges: int, num_keep: int,
                     keep_lowest: bool) -> np.ndarray:
     """core.py:233-240 verbatim: the reference's unstable argsort tie order."""

@@ -379,6 +379,38 @@ int gs_spanning_forest(gs_ctx *ctx, const double *scores, int s_loc, int64_t nsc
                        int keep_lowest, int expand, uint8_t *mask, int m_loc, int32_t *labels,
                        int l_loc, int64_t *n_forest, int64_t *n_marked, int32_t *rounds);
 
+/* ---- spectral sparsification by effective-resistance sampling ----------------
+ * Spielman-Srivastava sampling over the undirected pairs of the E columns of
+ * (src, dst); selection.spectral_sample is the definition and the result equals it
+ * bit for bit.  inverse = gs_undirected_ids' ids, *m = their count.  Pair j takes the
+ * score of its lowest column (scores[i] belongs to column i, nscores >= E); a loop
+ * and a score that is NaN, +-inf or <= 0 give the rate 0, and p = rate / np.sum(rate)
+ * (gs_sample_probs' blocked pairwise total).  rng is a Generator(PCG64) in the state
+ * (state_hi/lo, inc_hi/lo).
+ * method 0 (multinomial): cdf = cumsum(p) / cumsum(p)[-1]; draw j < q is double j of
+ * the stream, searched side='right' (== rng.choice(m, q, True, p)); counts[j] = the
+ * draws that landed on pair j, its weight counts / fl(q p).  *draws = q.
+ * method 1 (independent): pair j is kept (counts 1) when double j of the stream is
+ * < pk = min(1, fl(q p)), its weight 1 / pk; no cumsum.  *draws = m.
+ * mask[i] = counts[inverse[i]] > 0 and weight[i] = the pair's weight (0 where
+ * dropped), i < E; counts (optional, int64, room for E entries: the first *m are
+ * written) and inverse (optional, int64[E]); each buffer at its own *_loc.
+ * *n_kept_pairs = pairs with counts > 0, *max_count = the largest count,
+ * *n_irregular = the non-loop pairs that do not have exactly two columns (one
+ * direction only, duplicates: the weighted result would not be symmetric).
+ * *status: 0 = written; 1 = degenerate input and nothing was written: ids outside
+ * gs_undirected_ids' contract, nscores < E, a total that is not finite and positive,
+ * q outside [1, 2^31) -- the caller evaluates selection.spectral_sample on the host,
+ * so its exception surfaces.  GS_EINVAL: a method other than 0 / 1.
+ * Integer atomics only: the outputs are the same bytes on every run. */
+int gs_spectral_sample(gs_ctx *ctx, const double *scores, int s_loc, int64_t nscores,
+                       const int64_t *src, const int64_t *dst, int loc, int64_t E, int64_t n,
+                       int64_t q, int method, uint64_t state_hi, uint64_t state_lo,
+                       uint64_t inc_hi, uint64_t inc_lo, uint8_t *mask, int m_loc, double *weight,
+                       int w_loc, int64_t *counts, int c_loc, int64_t *inverse, int i_loc,
+                       int64_t *m, int64_t *n_kept_pairs, int64_t *max_count,
+                       int64_t *n_irregular, int64_t *draws, int32_t *status);
+
 int gs_metric_backbone(gs_ctx *ctx, int64_t n, int64_t E, const int64_t *src,
                        const int64_t *dst, const double *w, int64_t nw, int loc, double eps,
                        uint8_t *keep, int keep_loc, int64_t *n_relax);
