@@ -16,45 +16,17 @@
 // bits.  alpha and beta of the CG are formed on the device from the folds; a solve
 // that has met its tolerance freezes itself (its launches return at once), so the
 // host only polls every kCgPoll iterations.
+//
+// The Laplacian apply by row class (SpOp), the row classes, the chunk geometry and the
+// solve of L y = P v (sp_solve) are defined here and declared in gs_sp_solve.hpp, which
+// gs_spectral_bounds.hip shares; the folds are that header's.
 #include <cmath>
 
 #include "gs_dense.hpp"
 #include "gs_lanczos.hpp"
+#include "gs_sp_solve.hpp"
 
 namespace gs {
-
-static constexpr int kSpThreads = 256;
-static constexpr int kSpWaves = kSpThreads / 64;
-static constexpr int kSpMaxBlocks = 1024;  // partials per reduction (a fold reads them all)
-static constexpr int kSpShort = 32;        // rows up to this many entries: one lane each
-static constexpr int kSpWide = 512;        // rows above this: workgroups (else one wave each)
-static constexpr int kSpSeg = 2048;        // ... one per this many entries of the row
-static constexpr int kCgPoll = 8;          // the host reads the residual every this many iterations
-static constexpr int kLzMaxBasis = 512;    // >= max_iter + 1 coefficients in LDS: the basis and 1
-
-// slots of the CG's scalar block (doubles); RZ and RR are ping-pong pairs indexed by the
-// iteration's parity, so no launch reads a slot that one of its own workgroups writes
-enum { S_RZ = 0, S_RR = 2, S_THRESH = 4, S_RRNOW = 5, S_ITS = 6, S_COUNT = 8 };
-
-// sum over the workgroup, the same value in every thread: shuffles, then the waves' sums
-// left to right
-__device__ double sp_block_sum(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int w = 0; w < kSpWaves; ++w) s += red[w];
-    return s;
-}
-
-// the fixed fold of nb <= kSpMaxBlocks partials (every workgroup that needs the total
-// folds it itself, in this one order)
-__device__ double sp_fold(const double *__restrict__ part, int nb, double *red) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nb; i += kSpThreads) s += part[i];
-    return sp_block_sum(s, red);
-}
 
 // a solve that has met its tolerance: the residual of the current parity is below it
 __device__ bool cg_frozen(const double *scal, int par) {
@@ -177,16 +149,7 @@ __global__ void k_sp_invdeg(int64_t n, const double *__restrict__ deg, double *_
 }
 
 // ------------------------------------------------------------------ vector passes
-// Workgroup b owns elements [b chunk, min(n, (b + 1) chunk)) in every pass below.
-struct SpGeom {
-    int64_t n, chunk;
-    int nb;
-};
-
-#define SP_OWN(g)                                                        \
-    const int64_t lo = blockIdx.x * (g).chunk;                           \
-    const int64_t hi = lo + (g).chunk < (g).n ? lo + (g).chunk : (g).n
-
+// Workgroup b owns elements [b chunk, min(n, (b + 1) chunk)) in every pass below (SpGeom).
 // part[b] = sum of x over the chunk
 __global__ void __launch_bounds__(kSpThreads)
 k_sp_sum(SpGeom g, const double *__restrict__ x, double *__restrict__ part) {
@@ -448,37 +411,101 @@ k_sp_lz_next(SpGeom g, int64_t ldv, int j, double *__restrict__ V, const double 
 
 namespace {
 
-struct SpOp {
-    gs_ctx *c;
-    hipStream_t st;
-    int64_t n;
-    const int64_t *ip;
-    const int32_t *ix;
-    const double *d;
-    const int32_t *lwave, *lwide, *wbase, *segrow, *segoff;
-    int32_t nwave, nwide, nseg;
-    double *deg, *wpart;
-
-    // q = L p (DEG: q = the weighted degrees); scal / par: the solve whose freeze it obeys
-    template <bool DEG>
-    void apply(const double *p, double *q, const double *scal, int par) const {
-        hipEvent_t e = prof_begin(c);
-        k_sp_lap_short<DEG><<<grid_for(n, kSpThreads, 1 << 16), kSpThreads, 0, st>>>(
-            n, ip, ix, d, deg, p, q, scal, par);
-        if (nwave)
-            k_sp_lap_wave<DEG><<<(unsigned)((nwave + kSpWaves - 1) / kSpWaves), kSpThreads, 0, st>>>(
-                nwave, lwave, ip, ix, d, deg, p, q, scal, par);
-        if (nwide) {
-            k_sp_lap_seg<DEG><<<(unsigned)nseg, kSpThreads, 0, st>>>(segrow, segoff, ip, ix, d, p,
-                                                                    wpart, scal, par);
-            k_sp_lap_wide<DEG><<<grid_for(nwide, kSpThreads), kSpThreads, 0, st>>>(
-                nwide, lwide, wbase, ip, wpart, deg, p, q, scal, par);
-        }
-        prof_end(c, e, "fiedler_sparse_spmv", 0.0);
+// q = L p (DEG: q = the weighted degrees); scal / par: the solve whose freeze it obeys
+template <bool DEG>
+void sp_apply(const SpOp &o, const double *p, double *q, const double *scal, int par) {
+    hipEvent_t e = prof_begin(o.c);
+    k_sp_lap_short<DEG><<<grid_for(o.n, kSpThreads, 1 << 16), kSpThreads, 0, o.st>>>(
+        o.n, o.ip, o.ix, o.d, o.deg, p, q, scal, par);
+    if (o.nwave)
+        k_sp_lap_wave<DEG><<<(unsigned)((o.nwave + kSpWaves - 1) / kSpWaves), kSpThreads, 0, o.st>>>(
+            o.nwave, o.lwave, o.ip, o.ix, o.d, o.deg, p, q, scal, par);
+    if (o.nwide) {
+        k_sp_lap_seg<DEG><<<(unsigned)o.nseg, kSpThreads, 0, o.st>>>(o.segrow, o.segoff, o.ip, o.ix,
+                                                                    o.d, p, o.wpart, scal, par);
+        k_sp_lap_wide<DEG><<<grid_for(o.nwide, kSpThreads), kSpThreads, 0, o.st>>>(
+            o.nwide, o.lwide, o.wbase, o.ip, o.wpart, o.deg, p, q, scal, par);
     }
-};
+    prof_end(o.c, e, o.label, 0.0);
+}
 
 }  // namespace
+
+void SpOp::apply(const double *p, double *q, const double *scal, int par) const {
+    sp_apply<false>(*this, p, q, scal, par);
+}
+
+void SpOp::degrees(double *out) const { sp_apply<true>(*this, nullptr, out, nullptr, 0); }
+
+SpOp sp_row_classes(gs_ctx *c, const char *what) {
+    Graph &g = c->g;
+    const int64_t n = g.n;
+    hipStream_t st = c->stream;
+    // a wide row has more than kSpWide entries and at most len / kSpSeg + 1 segments, so
+    // there are fewer than nnz / kSpWide wide rows and nnz (1 / kSpSeg + 1 / kSpWide) segments
+    const size_t wcap = (size_t)(g.nnz / kSpWide + 1), scap = (size_t)(g.nnz / kSpSeg + 1) + wcap;
+    int32_t *cnt = (int32_t *)c->buf("fs_cnt").ensure(sizeof(int32_t) * 3);
+    int32_t *lwave = (int32_t *)c->buf("fs_lwave").ensure(sizeof(int32_t) * (size_t)n);
+    int32_t *lwide = (int32_t *)c->buf("fs_lwide").ensure(sizeof(int32_t) * 2 * wcap);
+    int32_t *wbase = lwide + wcap;
+    int32_t *segrow = (int32_t *)c->buf("fs_seg").ensure(sizeof(int32_t) * 2 * scap);
+    int32_t *segoff = segrow + scap;
+    double *wpart = (double *)c->buf("fs_wpart").ensure(sizeof(double) * scap);
+    GS_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * 3, st));
+    k_sp_classify<<<grid_for(n, kSpThreads, 1 << 16), kSpThreads, 0, st>>>(
+        n, g.indptr.as<int64_t>(), cnt, lwave, lwide, wbase, segrow, segoff);
+    GS_HIP(hipGetLastError());
+    int32_t hcnt[3] = {0, 0, 0};
+    GS_HIP(hipMemcpyAsync(hcnt, cnt, sizeof(hcnt), hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    GS_CHECK((size_t)hcnt[1] <= wcap && (size_t)hcnt[2] <= scap, GS_EHIP,
+             "%s: the wide-row tables overflowed", what);
+    return SpOp{c,      st,     n,       g.indptr.as<int64_t>(), g.indices.as<int32_t>(),
+                g.data.as<double>(), lwave, lwide, wbase, segrow, segoff, hcnt[0], hcnt[1],
+                hcnt[2], nullptr, wpart, nullptr};
+}
+
+void sp_inverse_degrees(const SpOp &op, const double *deg, double *inv) {
+    k_sp_invdeg<<<grid_for(op.n, kSpThreads, 1 << 16), kSpThreads, 0, op.st>>>(op.n, deg, inv);
+    GS_HIP(hipGetLastError());
+}
+
+bool sp_solve(const SpOp &op, const SpCg &cg, const double *v, double rtol, int32_t max_iter,
+              double h[S_COUNT]) {
+    gs_ctx *c = op.c;
+    hipStream_t st = op.st;
+    const SpGeom &geo = cg.geo;
+    const unsigned G = (unsigned)geo.nb;
+    double *part = cg.part, *part3 = cg.part + geo.nb;
+    hipEvent_t e = prof_begin(c);
+    k_sp_sum<<<G, kSpThreads, 0, st>>>(geo, v, part);
+    k_sp_xr<true><<<G, kSpThreads, 0, st>>>(geo, v, cg.p, cg.q, cg.inv, cg.x, cg.r, part, part3,
+                                            cg.scal, 0);
+    k_sp_p<true><<<G, kSpThreads, 0, st>>>(geo, cg.r, cg.inv, cg.p, part3, cg.scal, 0, rtol);
+    prof_end(c, e, cg.label, 0.0);
+    GS_HIP(hipGetLastError());
+    for (int i = 0; i < S_COUNT; ++i) h[i] = 0.0;
+    bool solved = false;
+    for (int32_t it = 0; it < max_iter && !solved;) {
+        const int32_t stop = std::min<int64_t>(max_iter, (int64_t)it + kCgPoll);
+        for (; it < stop; ++it) {
+            const int par = it & 1;
+            op.apply(cg.p, cg.q, cg.scal, par);
+            e = prof_begin(c);
+            k_sp_dot<<<G, kSpThreads, 0, st>>>(geo, cg.p, cg.q, part, cg.scal, par);
+            k_sp_xr<false><<<G, kSpThreads, 0, st>>>(geo, v, cg.p, cg.q, cg.inv, cg.x, cg.r, part,
+                                                     part3, cg.scal, par);
+            k_sp_p<false><<<G, kSpThreads, 0, st>>>(geo, cg.r, cg.inv, cg.p, part3, cg.scal, par,
+                                                    rtol);
+            prof_end(c, e, cg.label, 0.0);
+        }
+        GS_HIP(hipGetLastError());
+        GS_HIP(hipMemcpyAsync(h, cg.scal, sizeof(double) * S_COUNT, hipMemcpyDeviceToHost, st));
+        GS_HIP(hipStreamSynchronize(st));
+        solved = h[S_RRNOW] <= h[S_THRESH];
+    }
+    return solved;
+}
 
 void fiedler_sparse(gs_ctx *c, double tol, int32_t max_iter, double cg_rtol, int32_t cg_max_iter,
                     double *value, int32_t *iterations, int64_t *cg_iterations) {
@@ -494,43 +521,19 @@ void fiedler_sparse(gs_ctx *c, double tol, int32_t max_iter, double cg_rtol, int
     GS_CHECK(ncomp == 1, GS_EINVAL, "algebraic connectivity: graph has %lld components",
              (long long)ncomp);
 
-    SpGeom geo;
-    geo.n = n;
-    int64_t nb = std::min<int64_t>(kSpMaxBlocks, (n + kSpThreads - 1) / kSpThreads);
-    geo.chunk = ((n + nb - 1) / nb + kSpThreads - 1) / kSpThreads * kSpThreads;
-    geo.nb = (int)((n + geo.chunk - 1) / geo.chunk);
-    nb = geo.nb;
+    const SpGeom geo = sp_geometry(n);
+    const int64_t nb = geo.nb;
     const int64_t ldv = (n + 63) & ~(int64_t)63;
 
     // the rows by length, the weighted degrees and their reciprocals: once per call
-    // (a wide row has more than kSpWide entries and at most len / kSpSeg + 1 segments, so
-    // there are fewer than nnz / kSpWide wide rows and nnz (1 / kSpSeg + 1 / kSpWide) segments)
-    const size_t wcap = (size_t)(g.nnz / kSpWide + 1), scap = (size_t)(g.nnz / kSpSeg + 1) + wcap;
-    int32_t *cnt = (int32_t *)c->buf("fs_cnt").ensure(sizeof(int32_t) * 3);
-    int32_t *lwave = (int32_t *)c->buf("fs_lwave").ensure(sizeof(int32_t) * (size_t)n);
-    int32_t *lwide = (int32_t *)c->buf("fs_lwide").ensure(sizeof(int32_t) * 2 * wcap);
-    int32_t *wbase = lwide + wcap;
-    int32_t *segrow = (int32_t *)c->buf("fs_seg").ensure(sizeof(int32_t) * 2 * scap);
-    int32_t *segoff = segrow + scap;
-    double *wpart = (double *)c->buf("fs_wpart").ensure(sizeof(double) * scap);
     double *vec = (double *)c->buf("fs_vec").ensure(sizeof(double) * 6 * (size_t)n);
     double *deg = vec, *inv = vec + n, *x = vec + 2 * n, *r = vec + 3 * n, *p = vec + 4 * n,
            *q = vec + 5 * n;
-    GS_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * 3, st));
-    k_sp_classify<<<grid_for(n, kSpThreads, 1 << 16), kSpThreads, 0, st>>>(
-        n, g.indptr.as<int64_t>(), cnt, lwave, lwide, wbase, segrow, segoff);
-    GS_HIP(hipGetLastError());
-    int32_t hcnt[3] = {0, 0, 0};
-    GS_HIP(hipMemcpyAsync(hcnt, cnt, sizeof(hcnt), hipMemcpyDeviceToHost, st));
-    GS_HIP(hipStreamSynchronize(st));
-    GS_CHECK((size_t)hcnt[1] <= wcap && (size_t)hcnt[2] <= scap, GS_EHIP,
-             "algebraic connectivity: the wide-row tables overflowed");
-    const SpOp op{c,      st,     n,       g.indptr.as<int64_t>(), g.indices.as<int32_t>(),
-                  g.data.as<double>(), lwave, lwide, wbase, segrow, segoff, hcnt[0], hcnt[1],
-                  hcnt[2], deg, wpart};
-    op.apply<true>(nullptr, deg, nullptr, 0);
-    k_sp_invdeg<<<grid_for(n, kSpThreads, 1 << 16), kSpThreads, 0, st>>>(n, deg, inv);
-    GS_HIP(hipGetLastError());
+    SpOp op = sp_row_classes(c, "algebraic connectivity");
+    op.deg = deg;
+    op.label = "fiedler_sparse_spmv";
+    op.degrees(deg);
+    sp_inverse_degrees(op, deg, inv);
 
     double *V = (double *)c->buf("lz_V").ensure(sizeof(double) * (size_t)(max_iter + 1) * ldv);
     double *ab = (double *)c->buf("lz_ab").ensure(sizeof(double) * (3 * (size_t)max_iter + 8));
@@ -542,6 +545,7 @@ void fiedler_sparse(gs_ctx *c, double tol, int32_t max_iter, double cg_rtol, int
     double *cvec = (double *)c->buf("fs_c").ensure(sizeof(double) * kLzMaxBasis);
     double *scal = (double *)c->buf("fs_scal").ensure(sizeof(double) * S_COUNT);
 
+    const SpCg cg{geo, inv, x, r, p, q, part, scal, "fiedler_sparse_vector"};
     const unsigned G = (unsigned)nb;
     k_sp_start_raw<<<G, kSpThreads, 0, st>>>(geo, V, part);
     k_sp_start_centre<<<G, kSpThreads, 0, st>>>(geo, V, part, part3);
@@ -555,31 +559,8 @@ void fiedler_sparse(gs_ctx *c, double tol, int32_t max_iter, double cg_rtol, int
     for (int j = 0; j < max_iter; ++j) {
         const double *vj = V + (int64_t)j * ldv;
         // ---- L x = P v_j by Jacobi-preconditioned CG on the mean-free subspace
-        hipEvent_t e = prof_begin(c);
-        k_sp_sum<<<G, kSpThreads, 0, st>>>(geo, vj, part);
-        k_sp_xr<true><<<G, kSpThreads, 0, st>>>(geo, vj, p, q, inv, x, r, part, part3, scal, 0);
-        k_sp_p<true><<<G, kSpThreads, 0, st>>>(geo, r, inv, p, part3, scal, 0, cg_rtol);
-        prof_end(c, e, "fiedler_sparse_vector", 0.0);
-        GS_HIP(hipGetLastError());
-        double h[S_COUNT] = {0};
-        bool solved = false;
-        for (int32_t it = 0; it < cg_max_iter && !solved;) {
-            const int32_t stop = std::min<int64_t>(cg_max_iter, (int64_t)it + kCgPoll);
-            for (; it < stop; ++it) {
-                const int par = it & 1;
-                op.apply<false>(p, q, scal, par);
-                e = prof_begin(c);
-                k_sp_dot<<<G, kSpThreads, 0, st>>>(geo, p, q, part, scal, par);
-                k_sp_xr<false><<<G, kSpThreads, 0, st>>>(geo, vj, p, q, inv, x, r, part, part3, scal,
-                                                         par);
-                k_sp_p<false><<<G, kSpThreads, 0, st>>>(geo, r, inv, p, part3, scal, par, cg_rtol);
-                prof_end(c, e, "fiedler_sparse_vector", 0.0);
-            }
-            GS_HIP(hipGetLastError());
-            GS_HIP(hipMemcpyAsync(h, scal, sizeof(h), hipMemcpyDeviceToHost, st));
-            GS_HIP(hipStreamSynchronize(st));
-            solved = h[S_RRNOW] <= h[S_THRESH];
-        }
+        double h[S_COUNT];
+        const bool solved = sp_solve(op, cg, vj, cg_rtol, cg_max_iter, h);
         cg_total += (int64_t)h[S_ITS];
         if (!solved) {
             if (iterations) *iterations = j;
@@ -592,7 +573,7 @@ void fiedler_sparse(gs_ctx *c, double tol, int32_t max_iter, double cg_rtol, int
                      j, (int)cg_max_iter, rel, cg_rtol, j, (long long)cg_total);
         }
         // ---- the Lanczos step on w = x
-        e = prof_begin(c);
+        hipEvent_t e = prof_begin(c);
         k_sp_sum<<<G, kSpThreads, 0, st>>>(geo, x, part);
         k_sp_lz_alpha<<<G, kSpThreads, 0, st>>>(geo, vj, x, part, part3);
         k_sp_lz_rec<<<G, kSpThreads, 0, st>>>(geo, ldv, j, V, x, part3, al, be, cpart);

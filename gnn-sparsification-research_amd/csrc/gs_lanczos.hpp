@@ -1,12 +1,14 @@
 // gs_lanczos.hpp -- what the two forms of the algebraic connectivity share: the dense
 // one (gs_topology.hip: Lanczos on the Cholesky inverse, one workgroup per step) and
 // the sparse one (gs_fiedler_sparse.hip: Lanczos on preconditioned-CG solves, grid-wide
-// steps).  Both build the same tridiagonal T and read its largest eigenvalue the same way.
+// steps).  Both build the same tridiagonal T and read its largest eigenvalue the same way
+// (gs_tridiag.hpp, which the spectral bounds of gs_spectral_bounds.hip read both ends of).
 #pragma once
 
 #include <cmath>
 
 #include "gs_internal.hpp"
+#include "gs_tridiag.hpp"
 
 namespace gs {
 
@@ -16,35 +18,6 @@ static constexpr int64_t kFiedlerDenseMax = 32768;
 // ||r|| / ||P v_j|| and the iteration cap of one solve
 static constexpr double kFiedlerCgRtol = 1e-10;
 static constexpr int32_t kFiedlerCgMaxIter = 5000;
-
-// Sturm count: eigenvalues of the (m x m) tridiagonal (a, b) below x
-__device__ inline int lz_sturm(const double *a, const double *b, int m, double x) {
-    int cnt = 0;
-    double q = 1.0;
-    for (int i = 0; i < m; ++i) {
-        const double bb = i ? b[i - 1] * b[i - 1] : 0.0;
-        q = a[i] - x - (i ? bb / q : 0.0);
-        if (q == 0.0) q = 1e-300;
-        if (q < 0.0) ++cnt;
-    }
-    return cnt;
-}
-
-// largest eigenvalue of T (m x m): Gershgorin bracket, bisection (one thread)
-__device__ inline double lz_ritz_max(const double *al, const double *be, int m) {
-    double lo = 1e300, hi = -1e300;
-    for (int i = 0; i < m; ++i) {
-        const double r = (i ? fabs(be[i - 1]) : 0.0) + (i + 1 < m ? fabs(be[i]) : 0.0);
-        lo = fmin(lo, al[i] - r);
-        hi = fmax(hi, al[i] + r);
-    }
-    for (int it = 0; it < 200 && hi - lo > 1e-15 * fabs(hi); ++it) {
-        const double mid = 0.5 * (lo + hi);
-        if (lz_sturm(al, be, m, mid) < m) lo = mid;  // some eigenvalue above mid
-        else hi = mid;
-    }
-    return hi;
-}
 
 // element i of the fixed pseudo-random start vector, before the mean is removed and the
 // norm taken (deterministic)

@@ -17,8 +17,10 @@ from .metrics import (
     calculate_feature_cosine_scores,
     calculate_jaccard_scores,
     compute_geodesic_preservation,
+    compute_spectral_approximation,
     compute_topology_metrics,
     compute_topology_preservation,
+    spectral_bounds_dense,
 )
 from .random import RandomBaseline, precompute_random_scores, random_sparsify
 from .selection import spectral_sample
@@ -39,6 +41,8 @@ __all__ = [
     "compute_geodesic_preservation",
     "compute_topology_metrics",
     "compute_topology_preservation",
+    "compute_spectral_approximation",
+    "spectral_bounds_dense",
     "precompute_random_scores",
     "random_sparsify",
     "RandomBaseline",

@@ -126,6 +126,9 @@ SIGNATURES = {
     "gs_fiedler": (_int, [_vp, _f64, _i32, ctypes.POINTER(_f64), ctypes.POINTER(_i32)]),
     "gs_fiedler_sparse": (_int, [_vp, _f64, _i32, _f64, _i32, ctypes.POINTER(_f64),
                                  ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
+    "gs_spectral_bounds": (_int, [_vp, _vp, _int, _i64, _f64, _i32, _f64, _i32,
+                                  ctypes.POINTER(_f64), ctypes.POINTER(_f64),
+                                  ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
 }
 
 

@@ -385,6 +385,41 @@ class GraphSparsifier:
             return sparse_data, (mask.cpu(), weight.cpu())
         return sparse_data
 
+    def spectral_approximation(self, sparse, edge_weight=None, **caps) -> dict:
+        """How well a sparsifier of this graph approximates it spectrally (not in the
+        reference): ``metrics.compute_spectral_approximation`` of this graph's adjacency
+        and the sparsifier's, i.e. ``lambda_min``, ``lambda_max`` and ``epsilon`` of
+        ``(1 - epsilon) L_G <= L_H <= (1 + epsilon) L_G`` on the largest component.
+
+        ``sparse``: a ``Data`` returned by any ``sparsify_*`` method, or the ``(mask,
+        weight)`` pair ``sparsify_spectral(..., return_mask=True)`` returns (one entry per
+        ``edge_index`` column of this graph).  The weights are ``edge_weight`` when given
+        (one per column of ``sparse``), else ``Data.edge_weight`` when present, else 1.
+        Columns listing the same ordered pair add up, as they do in this graph's own
+        adjacency.  ``caps``: ``tol``, ``max_iter``, ``cg_rtol``, ``cg_max_iter``."""
+        from .metrics import compute_spectral_approximation
+
+        def host(t, dtype):
+            return np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=dtype)
+
+        if isinstance(sparse, (tuple, list)):
+            mask, weight = sparse
+            mask = host(mask, bool)
+            ei = host(self.data.edge_index, np.int64)[:, mask]
+            w = host(weight, np.float64)[mask]
+        else:
+            ei = host(sparse.edge_index, np.int64)
+            w = getattr(sparse, "edge_weight", None)
+            w = np.ones(ei.shape[1]) if w is None else host(w, np.float64)
+        if edge_weight is not None:
+            w = host(edge_weight, np.float64)
+        if w.shape != (ei.shape[1],):
+            raise ValueError(f"{w.shape} weights for {ei.shape[1]} columns")
+        n = self.num_nodes
+        sparse_adj = sp.csr_matrix((w, (ei[0], ei[1])), shape=(n, n))
+        sparse_adj.sum_duplicates()
+        return compute_spectral_approximation(self.adj, sparse_adj, **caps)
+
     def get_retention_curve_data(self, metric: str, retention_rates: list[float]) -> list[Data]:
         """core.py:463-480."""
         return [self.sparsify(metric, rate) for rate in retention_rates]

@@ -484,6 +484,44 @@ class Engine:
                 self.fiedler_cg_iterations = cg.value
         return v.value
 
+    def spectral_bounds(self, hw, tol: float = 1e-9, max_iter: int = 300,
+                        cg_rtol: float = 1e-10, cg_max_iter: int = 5000):
+        """gs_spectral_bounds: ``(lambda_min, lambda_max)`` of the pencil
+        ``L_H x = lambda L_G x`` over the mean-free vectors, G the (connected, symmetric)
+        resident graph and H the graph with weight ``hw[e]`` on CSR entry ``e`` of G (a
+        float64 numpy array or CUDA tensor of nnz entries in the order of ``Context.csr()``;
+        0 drops the entry, diagonal entries are ignored).  H is a ``(1 +- eps)`` spectral
+        approximation of G with ``eps = max(lambda_max - 1, 1 - lambda_min)``.
+
+        Lanczos on ``L_G^+ L_H`` in the ``L_G`` inner product, each step one
+        Jacobi-preconditioned CG solve to relative residual ``cg_rtol`` within
+        ``cg_max_iter`` iterations, until the residual bounds of both extreme Ritz pairs are
+        below ``tol * lambda_max`` or ``max_iter`` steps.  ``spectral_bounds_iterations``:
+        Lanczos steps; ``spectral_bounds_cg_iterations``: CG iterations of all solves.  A
+        solver that stops at a cap unconverged raises GsparseNotConverged (a RuntimeError);
+        the counts are recorded then too."""
+        if isinstance(hw, np.ndarray) or not hasattr(hw, "is_cuda"):
+            hw, loc = np.ascontiguousarray(hw, dtype=np.float64), GS_HOST
+        else:
+            import torch
+
+            hw = hw.detach().to(torch.float64).contiguous()
+            if hw.is_cuda:
+                loc = GS_DEVICE
+            else:
+                hw, loc = np.ascontiguousarray(hw.numpy()), GS_HOST
+        lo, hi = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        it, cg = ctypes.c_int32(0), ctypes.c_int64(0)
+        self.spectral_bounds_iterations = self.spectral_bounds_cg_iterations = None
+        try:
+            self.ctx.call("gs_spectral_bounds", ptr(hw), loc, int(hw.reshape(-1).shape[0]),
+                          float(tol), int(max_iter), float(cg_rtol), int(cg_max_iter),
+                          ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(it), ctypes.byref(cg))
+        finally:
+            self.spectral_bounds_iterations = it.value
+            self.spectral_bounds_cg_iterations = cg.value
+        return lo.value, hi.value
+
     # -- selection ------------------------------------------------------------
     def exact_er(self, out=None, method: str = "auto", cg_rtol: float = 1e-12,
                  cg_max_iter: int = 5000):

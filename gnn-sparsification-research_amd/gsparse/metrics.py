@@ -317,3 +317,107 @@ def compute_topology_preservation(original_adj: sp.csr_matrix, sparse_adj: sp.cs
         "original_metrics": orig_metrics,
         "sparse_metrics": sparse_metrics,
     }
+
+
+# ---- how good a sparsifier is: the spectral bounds of H against G ----------------------
+def _dense_laplacian(adj) -> np.ndarray:
+    A = adj.toarray() if sp.issparse(adj) else np.array(adj)
+    A = np.array(A, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError(f"adjacency must be square, got {A.shape}")
+    np.fill_diagonal(A, 0.0)  # a stored diagonal entry is no edge of L
+    return np.diag(A.sum(axis=1)) - A
+
+
+def spectral_bounds_dense(original_adj, sparse_adj):
+    """``(lambda_min, lambda_max)`` of the pencil ``L_H x = lambda L_G x`` on the range of
+    ``L_G``, G = ``original_adj`` and H = ``sparse_adj`` (both symmetric, dense or sparse):
+    the NumPy specification of ``compute_spectral_approximation``.
+
+    An ``eigh`` of ``L_G``, ``L_H`` whitened on the eigenvectors outside the null space
+    (``W = U / sqrt(lam)``, eigenvalues above ``1e-9 lam_max``), ``eigvalsh`` of
+    ``W' L_H W``.  ``O(n^3)`` time and ``O(n^2)`` memory: for small ``n`` and for tests."""
+    L = _dense_laplacian(original_adj)
+    L2 = _dense_laplacian(sparse_adj)
+    if L.shape != L2.shape:
+        raise ValueError(f"shape mismatch: {L.shape} and {L2.shape}")
+    lam, U = np.linalg.eigh(L)
+    keep = lam > 1e-9 * lam.max()
+    W = U[:, keep] / np.sqrt(lam[keep])
+    ev = np.linalg.eigvalsh(W.T @ L2 @ W)
+    return float(ev[0]), float(ev[-1])
+
+
+def _entry_keys(a: sp.csr_matrix) -> NDArray[np.int64]:
+    n = a.shape[0]
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(a.indptr))
+    return rows * n + a.indices.astype(np.int64)
+
+
+def _weights_on_support(a: sp.csr_matrix, b: sp.csr_matrix) -> NDArray[np.float64]:
+    """b's entries at a's canonical CSR positions (0 elsewhere); both canonical."""
+    ka, kb = _entry_keys(a), _entry_keys(b)
+    pos = np.searchsorted(ka, kb)
+    inside = pos < len(ka)
+    inside[inside] = ka[pos[inside]] == kb[inside]
+    if not inside.all():
+        e = int(np.flatnonzero(~inside)[0])
+        raise ValueError(f"sparse_adj entry ({kb[e] // a.shape[0]}, {kb[e] % a.shape[0]}) is "
+                         "outside the support of original_adj")
+    hw = np.zeros(a.nnz, dtype=np.float64)
+    hw[pos] = b.data
+    return hw
+
+
+def compute_spectral_approximation(original_adj, sparse_adj, tol: float = 1e-9,
+                                   max_iter: int = 300, cg_rtol: float = 1e-10,
+                                   cg_max_iter: int = 5000) -> Dict:
+    """How well ``sparse_adj`` (H: a reweighted subgraph) approximates ``original_adj`` (G)
+    spectrally (not in the reference): the extreme eigenvalues of ``L_H x = lambda L_G x``
+    over the mean-free vectors, on the device (``gs_spectral_bounds``: Lanczos on
+    ``L_G^+ L_H``, each step a Jacobi-preconditioned CG solve).  H is a ``(1 +- epsilon)``
+    approximation of G with ``epsilon = max(lambda_max - 1, 1 - lambda_min)``;
+    ``lambda_min`` is 0 exactly when H disconnects what G connects.
+
+    Both graphs are symmetric with non-negative entries (NotImplementedError otherwise),
+    of the same shape, and every entry of ``sparse_adj`` lies on an entry of
+    ``original_adj`` (ValueError otherwise); stored diagonal entries are ignored.  Both are
+    restricted to the original's largest component (ties: the one with the smallest node
+    id, as in ``compute_topology_metrics``), which must have at least two nodes.
+
+    Returns ``lambda_min``, ``lambda_max``, ``epsilon``, ``nodes`` (of that component),
+    ``num_connected_components`` (of the original), ``iterations`` (Lanczos steps) and
+    ``cg_iterations``.  A solver that stops at ``max_iter`` or ``cg_max_iter`` unconverged
+    raises RuntimeError (``GsparseNotConverged``); no value is made up."""
+    a, _ = _prepare(original_adj)
+    b, _ = _prepare(sparse_adj)
+    if a.shape != b.shape:
+        raise ValueError(f"shape mismatch: original {a.shape}, sparse {b.shape}")
+    _weights_on_support(a, b)  # the support check, before the device is touched
+    n = a.shape[0]
+    ctx = _scratch_context()
+    ctx.set_graph_csr(n, a.indptr, a.indices, a.data)
+    eng = Engine(ctx)
+    labels, num_components, _ = eng.components() if n > 0 else (np.zeros(0), 0, 0)
+    if num_components > 1:
+        roots, sizes = np.unique(labels, return_counts=True)
+        nodes = np.flatnonzero(labels == roots[np.argmax(sizes)])
+        a = a[nodes][:, nodes].tocsr()
+        b = b[nodes][:, nodes].tocsr()
+        a.sort_indices()
+        b.sort_indices()
+        ctx.set_graph_csr(a.shape[0], a.indptr, a.indices, a.data)
+        eng = Engine(ctx)
+    hw = _weights_on_support(a, b)
+    lo, hi = eng.spectral_bounds(hw, tol=tol, max_iter=max_iter, cg_rtol=cg_rtol,
+                                 cg_max_iter=cg_max_iter)
+    its, cg = eng.spectral_bounds_iterations, eng.spectral_bounds_cg_iterations
+    return {
+        "lambda_min": lo,
+        "lambda_max": hi,
+        "epsilon": max(hi - 1.0, 1.0 - lo),
+        "nodes": int(a.shape[0]),
+        "num_connected_components": int(num_components),
+        "iterations": its,
+        "cg_iterations": cg,
+    }

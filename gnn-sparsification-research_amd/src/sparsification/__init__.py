@@ -8,8 +8,10 @@ from gsparse import (  # noqa: F401
     calculate_feature_cosine_scores,
     calculate_jaccard_scores,
     compute_geodesic_preservation,
+    compute_spectral_approximation,
     compute_topology_metrics,
     compute_topology_preservation,
+    spectral_bounds_dense,
     precompute_random_scores,
     random_sparsify,
 )
@@ -24,6 +26,8 @@ __all__ = [
     "compute_geodesic_preservation",
     "compute_topology_metrics",
     "compute_topology_preservation",
+    "compute_spectral_approximation",
+    "spectral_bounds_dense",
     "precompute_random_scores",
     "random_sparsify",
 ]

@@ -7,6 +7,8 @@ from gsparse.metrics import (  # noqa: F401
     calculate_feature_cosine_scores,
     calculate_jaccard_scores,
     compute_geodesic_preservation,
+    compute_spectral_approximation,
     compute_topology_metrics,
     compute_topology_preservation,
+    spectral_bounds_dense,
 )

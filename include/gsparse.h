@@ -577,6 +577,37 @@ int gs_fiedler_sparse(gs_ctx *ctx, double tol, int32_t max_iter, double cg_rtol,
                       int32_t cg_max_iter, double *value, int32_t *iterations,
                       int64_t *cg_iterations);
 
+/* ---- how good a sparsifier is: the spectral bounds of H against G ----------
+ * G is the resident graph (symmetric, connected, non-negative weights; stored
+ * diagonal entries are no part of L_G, as in gs_fiedler_sparse).  H is a graph
+ * on the same nodes whose support is a subset of G's: hw[e] is its weight on
+ * CSR entry e of G (nhw == nnz entries in the order gs_graph_copy_csr returns,
+ * hw_loc: GS_HOST / GS_DEVICE), 0 for a dropped entry; diagonal entries are
+ * ignored.  The outputs are the extreme eigenvalues of L_H x = lambda L_G x
+ * over the mean-free vectors,
+ *   lambda_min = min x'L_H x / x'L_G x,  lambda_max = max x'L_H x / x'L_G x,
+ * so H is a (1 +- eps) spectral approximation of G with
+ * eps = max(lambda_max - 1, 1 - lambda_min); lambda_min = 0 exactly when H
+ * disconnects what G connects.  Lanczos on L_G^+ L_H in the L_G inner product
+ * with full reorthogonalisation, each step one CG solve with L_G
+ * (Jacobi-preconditioned, relative residual cg_rtol within cg_max_iter
+ * iterations), until the residual bounds beta_j |s_last| of both extreme Ritz
+ * pairs are <= tol lambda_max, beta_j falls to the level of the solve's
+ * accuracy (an invariant subspace), or max_iter (<= 500) steps.  Defaults of the
+ * Python layer: tol 1e-9, max_iter 300, cg_rtol 1e-10, cg_max_iter 5000.
+ * Reductions are two-stage in a fixed order: two calls give the same bits.
+ * GS_EINVAL: nhw != nnz, several components, n < 2, max_iter outside [2, 500],
+ * cg_rtol outside (0, 1), cg_max_iter < 1, tol <= 0, an hw entry that is
+ * negative or not finite.  GS_EUNSUPPORTED: a directed adjacency, or
+ * hw[e] != hw[tpos[e]] bitwise.  GS_ENOCONV when a solve stops at cg_max_iter
+ * or Lanczos at max_iter unconverged: both outputs are then left untouched.
+ * *iterations (Lanczos steps) and *cg_iterations (inner iterations of all
+ * solves) are written in both cases; each output may be NULL. */
+int gs_spectral_bounds(gs_ctx *ctx, const double *hw, int hw_loc, int64_t nhw, double tol,
+                       int32_t max_iter, double cg_rtol, int32_t cg_max_iter,
+                       double *lambda_min, double *lambda_max, int32_t *iterations,
+                       int64_t *cg_iterations);
+
 #ifdef __cplusplus
 }
 #endif
