@@ -338,16 +338,22 @@ class Context:
     # ---- graph -----------------------------------------------------------
     def set_graph_edge_index(self, n: int, src, dst):
         """src/dst: int64 numpy arrays (host) or torch int64 CUDA tensors."""
-        loc = GS_HOST if isinstance(src, np.ndarray) else GS_DEVICE
-        E = int(src.shape[0])
+        from . import _args
+
+        src, dst, E, loc = _args.pair(src, dst, self.device, cast="host")
         self.call("gs_graph_from_edge_index", n, E, ptr(src), ptr(dst), loc)
 
     def set_graph_csr(self, n: int, indptr: np.ndarray, indices: np.ndarray,
                       data: np.ndarray | None):
-        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        from . import _args
+
+        (indptr, a), (indices, b) = (_args.inp(indptr, np.int64, "indptr", self.device, n + 1),
+                                     _args.inp(indices, np.int32, "indices", self.device))
+        c = GS_HOST
         if data is not None:
-            data = np.ascontiguousarray(data, dtype=np.float64)
+            data, c = _args.inp(data, np.float64, "data", self.device, indices.shape[0])
+        if (a, b, c) != (GS_HOST,) * 3:
+            raise ValueError("indptr, indices and data must be host arrays")
         self._keep = (indptr, indices, data)
         self.call("gs_graph_from_csr", n, int(indices.shape[0]), ptr(indptr), ptr(indices),
                   ptr(data), GS_HOST)

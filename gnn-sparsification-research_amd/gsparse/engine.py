@@ -17,126 +17,13 @@ import threading
 
 import numpy as np
 
-from . import _lib
+from . import _args as A
 from ._lib import GS_DEVICE, GS_HOST, Context, ptr
+from .plans import (OPENBLAS_MAX_THREADS, aa_weights, bb_geometry,  # noqa: F401 (re-exported)
+                    blas_threads_default, er_plan, er_reg_layout, er_reg_layout_w, er_split,
+                    jl_dim, xer_sparse_plan)
 
 _ROW_CHUNK_BYTES = 64 << 20
-
-
-def blas_threads_default() -> int:
-    """OpenBLAS thread count NumPy would use for np.dot in this process.
-
-    The reference's CG dot products are OpenBLAS ddot calls whose reduction
-    order depends on it (n > 10000); GSPARSE_BLAS_THREADS overrides.  Clamped to
-    OpenBLAS's MAX_THREADS (64 in NumPy's build), as OpenBLAS itself does."""
-    return min(_blas_threads_requested(), OPENBLAS_MAX_THREADS)
-
-
-OPENBLAS_MAX_THREADS = 64
-
-
-def _blas_threads_requested() -> int:
-    env = os.environ.get("GSPARSE_BLAS_THREADS")
-    if env:
-        return max(1, int(env))
-    try:
-        from threadpoolctl import threadpool_info
-
-        for info in threadpool_info():
-            if info.get("internal_api") == "openblas":
-                return max(1, int(info.get("num_threads", 1)))
-    except Exception:
-        pass
-    env = os.environ.get("OPENBLAS_NUM_THREADS")
-    return max(1, int(env)) if env else 1
-
-
-def jl_dim(n: int, epsilon: float) -> int:
-    """metrics.py:248, evaluated with NumPy exactly as the reference does."""
-    return max(int(24 * np.log(max(n, 2)) / (epsilon ** 2)), 1)
-
-
-def aa_weights(indptr: np.ndarray) -> np.ndarray:
-    """metrics.py:100-108 (adj_binary degrees -> c), NumPy ufuncs as the reference."""
-    degrees = np.diff(indptr).astype(np.float64)
-    log_degrees = np.log(degrees + 1)
-    log_degrees = np.maximum(log_degrees, 1e-10)
-    return 1.0 / np.sqrt(log_degrees)
-
-
-def er_split(k: int, parts: int) -> list[int]:
-    b = np.zeros(parts + 1, dtype=np.int64)
-    _lib.check(_lib.lib().gs_er_split(k, parts, ptr(b)), "gs_er_split")
-    return b.tolist()
-
-
-def er_plan(n: int, lnnz: int, ncols: int, blas_threads: int) -> dict:
-    """The plan gs_er_solve follows for ncols columns of an n-row system whose L_reg
-    has lnnz entries, under the GSPARSE_CG_* / _RES_* / _REG_* variables as they are
-    now (gs_er_plan; host code, no device): solver mode, columns per lane, chain rows
-    per trip, BLAS chunks."""
-    o = np.zeros(4, dtype=np.int32)
-    _lib.check(_lib.lib().gs_er_plan(n, lnnz, ncols, blas_threads, ptr(o)), "gs_er_plan")
-    return dict(zip(("mode", "cpl", "ru", "chunks"), o.tolist()))
-
-
-def er_reg_layout(n: int, blas_threads: int, unit: bool = True) -> dict | None:
-    """Where the register-resident solver (mode 5) keeps p for an n-row system, under
-    GSPARSE_REG_NT / GSPARSE_REG_KEEP as they are now (gs_er_reg_layout; host code, no
-    device); None where mode 5 does not apply.  threads per workgroup, G threads per
-    chain, R row slots per thread, T chunks, zslot (the LDS slots of p), dsl diagonal
-    slots, lds_bytes of a launch, and per chunk: start, len, its first keep rows in LDS
-    from LDS slot lbase."""
-    o = np.zeros(72, dtype=np.int64)
-    _lib.check(_lib.lib().gs_er_reg_layout(n, blas_threads, int(bool(unit)), ptr(o)),
-               "gs_er_reg_layout")
-    if o[0] == 0:
-        return None
-    d = dict(zip(("threads", "G", "R", "T", "zslot", "dsl", "lds_bytes"), o[:7].tolist()))
-    T = d["T"]
-    for i, name in enumerate(("start", "len", "keep", "lbase")):
-        d[name] = o[8 + 16 * i:8 + 16 * i + T].tolist()
-    return d
-
-
-def er_reg_layout_w(n: int, blas_threads: int, window: int, unit: bool = True) -> dict | None:
-    """er_reg_layout with a p window of ``window`` wave-slots per chunk asked for (3 or 4;
-    gs_er_reg_layout_w): also W, the window laid out -- 0 where the window kernel does
-    not exist (other than two threads per chain, weighted) or a prefix is not a whole
-    number of wave-slots, and the layout is then er_reg_layout's -- and per chunk wbase,
-    the LDS slot its window starts at."""
-    o = np.zeros(88, dtype=np.int64)
-    _lib.check(_lib.lib().gs_er_reg_layout_w(n, blas_threads, int(bool(unit)), int(window), ptr(o)),
-               "gs_er_reg_layout_w")
-    if o[0] == 0:
-        return None
-    d = dict(zip(("threads", "G", "R", "T", "zslot", "dsl", "lds_bytes", "W"), o[:8].tolist()))
-    T = d["T"]
-    for i, name in enumerate(("start", "len", "keep", "lbase", "wbase")):
-        d[name] = o[8 + 16 * i:8 + 16 * i + T].tolist()
-    return d
-
-
-def xer_sparse_plan(n: int, cus: int = 0) -> dict:
-    """The plan the sparse exact effective resistance (gs_exact_er_sparse) follows for an
-    n-node graph on a device of ``cus`` compute units (0: 256), under GSPARSE_XER_BATCH
-    as it is now (gs_xer_sparse_plan; host code, no device): batch, the columns solved
-    at a time (a multiple of 64); budget_bytes, what its four n x batch fp64 blocks may
-    take; chunks and chunk_rows, the row chunks of its reductions (functions of n alone)."""
-    o = np.zeros(4, dtype=np.int64)
-    _lib.check(_lib.lib().gs_xer_sparse_plan(int(n), int(cus), ptr(o)), "gs_xer_sparse_plan")
-    return dict(zip(("batch", "budget_bytes", "chunks", "chunk_rows"), o.tolist()))
-
-
-def bb_geometry(n: int, nsrc: int, nranks: int = 1, lpart: int = 0) -> dict:
-    """The numbers a metric backbone run of n nodes (E > 0) takes on rank lpart of nranks,
-    under the GSPARSE_BB_* variables as they are now (gs_bb_geometry; host code, no
-    device): K landmarks, whether their searches spread over the GPU and with how many
-    workgroups each (lm_W, 0 when this rank has no landmark), and for nsrc sources with
-    open columns the sources per workgroup, its threads, the batches and the slabs."""
-    o = np.zeros(7, dtype=np.int64)
-    _lib.check(_lib.lib().gs_bb_geometry(n, nsrc, nranks, lpart, ptr(o)), "gs_bb_geometry")
-    return dict(zip(("K", "lm_coop", "lm_W", "S", "threads", "nbatch", "slabs"), o.tolist()))
 
 
 class Engine:
@@ -155,22 +42,20 @@ class Engine:
             self._indptr = ip
         return self._indptr
 
-    def _out(self, e0, e1, out):
-        if out is None:
-            return np.empty(e1 - e0, dtype=np.float64), GS_HOST
-        return out, (GS_HOST if isinstance(out, np.ndarray) else GS_DEVICE)
+    def _scores_out(self, count, out):
+        return A.out(out, np.float64, count, "out", self.ctx.device)
 
     # -- scorers ------------------------------------------------------------
     def jaccard(self, e0: int = 0, e1: int | None = None, out=None):
         e1 = self.nnz if e1 is None else e1
-        o, loc = self._out(e0, e1, out)
+        o, loc = self._scores_out(e1 - e0, out)
         self.ctx.call("gs_jaccard", e0, e1, ptr(o), loc)
         return o
 
     def jaccard_part(self, part: int, nparts: int, out=None):
         """Share `part` of `nparts` of the whole Jaccard vector (zeros elsewhere;
         the shares sum to jaccard()) -- gs_jaccard_part."""
-        o, loc = self._out(0, self.nnz, out)
+        o, loc = self._scores_out(self.nnz, out)
         self.ctx.call("gs_jaccard_part", part, nparts, ptr(o), loc)
         return o
 
@@ -189,70 +74,51 @@ class Engine:
             raise ValueError(f"bad part {part} of {nparts}")
         _, oo = self.jaccard_shares(nparts)
         cnt = int(oo[part + 1] - oo[part])
-        if out is None:
-            o, loc = np.empty(cnt, dtype=np.uint32), GS_HOST
-        else:
-            if out.numel() < cnt:
-                raise IndexError(f"counts buffer holds {out.numel()} < {cnt} values")
-            o, loc = out, GS_DEVICE
+        o, loc = A.out(out, (np.uint32, np.int32), cnt, "counts buffer", self.ctx.device,
+                       short=IndexError)
         self.ctx.call("gs_jaccard_part_counts", part, nparts, ptr(o), loc)
         return o
 
     def jaccard_from_counts(self, nparts: int, counts, stride: int, out=None):
         """gs_jaccard_from_counts: every part's counts (part p at p * stride) ->
         the Jaccard score of every CSR entry."""
-        cloc = GS_HOST if isinstance(counts, np.ndarray) else GS_DEVICE
-        if cloc == GS_HOST:
-            counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        if counts.shape[0] < nparts * stride:
-            raise IndexError(f"counts hold {counts.shape[0]} < {nparts} x {stride} values")
-        o, loc = self._out(0, self.nnz, out)
+        counts, cloc = A.inp(counts, (np.uint32, np.int32), "counts", self.ctx.device,
+                             nparts * stride, short=IndexError)
+        o, loc = self._scores_out(self.nnz, out)
         self.ctx.call("gs_jaccard_from_counts", nparts, ptr(counts), stride, cloc, ptr(o), loc)
         return o
 
     # -- distributed Jaccard-T select (gs_jsel_*, include/gsparse.h) ---------
     JSEL_BINS, JSEL_PASSES = 8192, 5
 
-    @staticmethod
-    def _loc(a):
-        if isinstance(a, np.ndarray):
-            return GS_HOST
-        return GS_DEVICE if a.is_cuda else GS_HOST
-
-    @staticmethod
-    def _need(a, count, dtypes, what):
-        n = a.size if isinstance(a, np.ndarray) else a.numel()
-        dt = a.dtype if isinstance(a, np.ndarray) else a.dtype
-        if dt not in dtypes:
-            raise TypeError(f"{what} must be one of {dtypes}, got {dt}")
-        if n < count:
-            raise IndexError(f"{what} holds {n} < {count} values")
-
     def jsel_begin(self, part: int, nparts: int, counts, num_keep: int, keep_lowest: bool, hist,
                    scores=None):
         """Keys (and, into ``scores``, the fp64 scores) of this part's owner pairs and the
         first weighted histogram into ``hist`` (JSEL_BINS int64/uint64 values)."""
-        import torch
-
+        dev = self.ctx.device
         _, oo = self.jaccard_shares(nparts)
         np_ = int(oo[part + 1] - oo[part])
-        self._need(counts, np_, (np.uint32, np.int32, torch.int32), "counts")
-        self._need(hist, self.JSEL_BINS, (np.uint64, np.int64, torch.int64), "hist")
-        if self._loc(hist) != GS_DEVICE:
+        counts, cloc = A.inp(counts, (np.uint32, np.int32), "counts", dev, np_, cast="never",
+                             short=IndexError)
+        hist, hloc = self._jsel_hist(hist)
+        if hloc != GS_DEVICE:
             raise ValueError("hist must be a device tensor (the ranks all-reduce it there)")
         sloc = GS_HOST
         if scores is not None:
-            self._need(scores, np_, (np.float64, torch.float64), "scores")
-            sloc = self._loc(scores)
-        self.ctx.call("gs_jsel_begin", int(part), int(nparts), ptr(counts), self._loc(counts),
+            scores, sloc = A.out(scores, np.float64, np_, "scores", dev, short=IndexError)
+        self.ctx.call("gs_jsel_begin", int(part), int(nparts), ptr(counts), cloc,
                       int(num_keep), int(bool(keep_lowest)), ptr(hist), ptr(scores), sloc)
         self._jsel_pairs = np_
         return np_
 
+    def _jsel_hist(self, hist):
+        return A.out(hist, (np.int64, np.uint64), self.JSEL_BINS, "hist", self.ctx.device,
+                     short=IndexError)
+
     def jsel_step(self, hist) -> int:
         """One pass of the select on the all-reduced ``hist``; returns the passes left."""
         left = ctypes.c_int(0)
-        self.ctx.call("gs_jsel_step", ptr(hist), ctypes.byref(left))
+        self.ctx.call("gs_jsel_step", ptr(self._jsel_hist(hist)[0]), ctypes.byref(left))
         return left.value
 
     def jsel_result(self):
@@ -264,73 +130,54 @@ class Engine:
 
     def jsel_tie_positions(self, out):
         """This rank's tied CSR positions into ``out`` (int64)."""
-        import torch
-
-        self._need(out, 0, (np.int64, torch.int64), "positions")
-        n = out.size if isinstance(out, np.ndarray) else out.numel()
-        self.ctx.call("gs_jsel_tie_positions", ptr(out), int(n), self._loc(out))
+        out, loc = A.out(out, np.int64, 0, "positions", self.ctx.device)
+        self.ctx.call("gs_jsel_tie_positions", ptr(out), A.size(out), loc)
         return out
 
     def jsel_keep(self, tie_pos, ntie: int, need: int, out):
         """2-bit keep codes of this part's pairs (bit 0 owner entry, bit 1 reverse entry),
         four pairs per byte, into ``out`` (uint8, >= ceil(pairs / 4) bytes)."""
-        import torch
-
+        dev = self.ctx.device
         np_ = getattr(self, "_jsel_pairs", 0)
-        self._need(out, (np_ + 3) // 4, (np.uint8, torch.uint8), "keep")
+        out, loc = A.out(out, np.uint8, (np_ + 3) // 4, "keep", dev, short=IndexError)
         tloc = GS_HOST
         if tie_pos is not None:
-            self._need(tie_pos, ntie, (np.int64, torch.int64), "tie positions")
-            tloc = self._loc(tie_pos)
-        self.ctx.call("gs_jsel_keep", ptr(tie_pos), int(ntie), tloc, int(need), ptr(out), self._loc(out))
+            tie_pos, tloc = A.inp(tie_pos, np.int64, "tie positions", dev, ntie, cast="never",
+                                  short=IndexError)
+        self.ctx.call("gs_jsel_keep", ptr(tie_pos), int(ntie), tloc, int(need), ptr(out), loc)
         return out
 
     def jsel_mask(self, nparts: int, keep_all, stride: int, out):
         """Every part's keep codes (part p's from byte p * stride) -> the CSR keep mask (uint8)."""
-        import torch
-
-        self._need(keep_all, nparts * stride, (np.uint8, torch.uint8), "keep_all")
-        self._need(out, self.nnz, (np.uint8, torch.uint8, torch.bool), "mask")
-        self.ctx.call("gs_jsel_mask", int(nparts), ptr(keep_all), int(stride), self._loc(keep_all),
-                      ptr(out), self._loc(out))
+        dev = self.ctx.device
+        keep_all, kloc = A.inp(keep_all, np.uint8, "keep_all", dev, nparts * stride, cast="never",
+                               short=IndexError)
+        out, loc = A.out(out, (np.uint8, np.bool_), self.nnz, "mask", dev, short=IndexError)
+        self.ctx.call("gs_jsel_mask", int(nparts), ptr(keep_all), int(stride), kloc, ptr(out), loc)
         return out
 
     def adamic_adar(self, e0: int = 0, e1: int | None = None, out=None, c=None):
         e1 = self.nnz if e1 is None else e1
-        if c is None:
-            c = np.ascontiguousarray(aa_weights(self.indptr()))
-        o, loc = self._out(e0, e1, out)
-        cloc = GS_HOST if isinstance(c, np.ndarray) else GS_DEVICE
+        c, cloc = A.inp(aa_weights(self.indptr()) if c is None else c, np.float64, "c",
+                        self.ctx.device, self.n)
+        o, loc = self._scores_out(e1 - e0, out)
         self.ctx.call("gs_adamic_adar", ptr(c), cloc, e0, e1, ptr(o), loc)
         return o
 
     def degree(self, e0: int = 0, e1: int | None = None, out=None):
         e1 = self.nnz if e1 is None else e1
-        o, loc = self._out(e0, e1, out)
+        o, loc = self._scores_out(e1 - e0, out)
         self.ctx.call("gs_degree", e0, e1, ptr(o), loc)
         return o
 
     def feature_cosine(self, x, e0: int = 0, e1: int | None = None, out=None):
         """x: (n, f) float32/float64 numpy array or CUDA torch tensor."""
         e1 = self.nnz if e1 is None else e1
-        if isinstance(x, np.ndarray):
-            xloc = GS_HOST
-            x = np.ascontiguousarray(x)
-            dt = x.dtype
-        else:
-            xloc = GS_DEVICE if x.is_cuda else GS_HOST
-            x = x.contiguous()
-            if xloc == GS_HOST:
-                x = x.numpy()
-                dt = x.dtype
-            else:
-                import torch
-
-                dt = {torch.float32: np.dtype(np.float32),
-                      torch.float64: np.dtype(np.float64)}.get(x.dtype)
+        x, xloc = A.inp(x, None, "features", self.ctx.device)
+        dt = A.dtype_of(x)
         if x.ndim != 2 or x.shape[0] != self.n:
             raise ValueError(f"features must be ({self.n}, f), got {tuple(x.shape)}")
-        o, loc = self._out(e0, e1, out)
+        o, loc = self._scores_out(e1 - e0, out)
         if dt == np.float32:
             self.ctx.call("gs_feature_cosine_f32", ptr(x), int(x.shape[1]), xloc, e0, e1, ptr(o), loc)
         elif dt == np.float64:
@@ -386,7 +233,7 @@ class Engine:
     def er_scores(self, col0: int, col1: int, finalize: bool = True, e0: int = 0,
                   e1: int | None = None, out=None):
         e1 = self.nnz if e1 is None else e1
-        o, loc = self._out(e0, e1, out)
+        o, loc = self._scores_out(e1 - e0, out)
         self.ctx.call("gs_er_scores", col0, col1, e0, e1, int(finalize), ptr(o), loc)
         return o
 
@@ -432,7 +279,7 @@ class Engine:
     # -- topology analytics (compute_topology_metrics, metrics.py:445-520) ----
     def common_neighbors(self, out=None):
         """gs_common_neighbors: |N(u) ∩ N(v)| per CSR entry (symmetric graph)."""
-        o, loc = self._out(0, self.nnz, out)
+        o, loc = self._scores_out(self.nnz, out)
         self.ctx.call("gs_common_neighbors", ptr(o), loc)
         return o
 
@@ -500,21 +347,12 @@ class Engine:
         Lanczos steps; ``spectral_bounds_cg_iterations``: CG iterations of all solves.  A
         solver that stops at a cap unconverged raises GsparseNotConverged (a RuntimeError);
         the counts are recorded then too."""
-        if isinstance(hw, np.ndarray) or not hasattr(hw, "is_cuda"):
-            hw, loc = np.ascontiguousarray(hw, dtype=np.float64), GS_HOST
-        else:
-            import torch
-
-            hw = hw.detach().to(torch.float64).contiguous()
-            if hw.is_cuda:
-                loc = GS_DEVICE
-            else:
-                hw, loc = np.ascontiguousarray(hw.numpy()), GS_HOST
+        hw, loc = A.inp(hw, np.float64, "hw", self.ctx.device, cast="both")
         lo, hi = ctypes.c_double(0.0), ctypes.c_double(0.0)
         it, cg = ctypes.c_int32(0), ctypes.c_int64(0)
         self.spectral_bounds_iterations = self.spectral_bounds_cg_iterations = None
         try:
-            self.ctx.call("gs_spectral_bounds", ptr(hw), loc, int(hw.reshape(-1).shape[0]),
+            self.ctx.call("gs_spectral_bounds", ptr(hw), loc, A.size(hw),
                           float(tol), int(max_iter), float(cg_rtol), int(cg_max_iter),
                           ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(it), ctypes.byref(cg))
         finally:
@@ -545,7 +383,7 @@ class Engine:
         self.exact_er_iterations = self.exact_er_cg_iterations = None
         if method == "dense" and self.n > 32768:
             raise NotImplementedError(f"the dense exact effective resistance is O(n^3): n={self.n}")
-        o, loc = self._out(0, self.nnz, out)
+        o, loc = self._scores_out(self.nnz, out)
         it, cg = ctypes.c_int32(0), ctypes.c_int64(0)
         sparse = method == "sparse"
         try:
@@ -563,11 +401,11 @@ class Engine:
     def segment_argmax(self, scores: np.ndarray, src: np.ndarray, num_nodes: int) -> np.ndarray:
         """gs_segment_argmax: per node the column of its unique top score, -1 (no
         column) or -2 (np.argsort's order decides)."""
-        scores = np.ascontiguousarray(scores, dtype=np.float64)
-        src = np.ascontiguousarray(src, dtype=np.int64)
+        scores, sloc = A.inp(scores, np.float64, "scores", self.ctx.device)
+        src, loc = A.inp(src, np.int64, "src", self.ctx.device, cast="both")
         pick = np.empty(max(num_nodes, 1), dtype=np.int64)
-        self.ctx.call("gs_segment_argmax", ptr(scores), GS_HOST, int(scores.shape[0]), ptr(src),
-                      GS_HOST, int(src.shape[0]), int(num_nodes), ptr(pick), GS_HOST)
+        self.ctx.call("gs_segment_argmax", ptr(scores), sloc, int(scores.shape[0]), ptr(src),
+                      loc, int(src.shape[0]), int(num_nodes), ptr(pick), GS_HOST)
         return pick[:num_nodes]
 
     SEGK_CLASSES = ("empty", "all", "short", "lds", "stream")
@@ -580,8 +418,8 @@ class Engine:
         (decided) or 2 (np.argsort's order decides: no byte of that node is set);
         ``info`` = ``n_guaranteed``, ``n_ambiguous`` and ``classes`` (nodes handled
         per kernel class, keyed by SEGK_CLASSES)."""
-        scores = np.ascontiguousarray(scores, dtype=np.float64)
-        src = np.ascontiguousarray(src, dtype=np.int64)
+        scores, sloc = A.inp(scores, np.float64, "scores", self.ctx.device)
+        src, loc = A.inp(src, np.int64, "src", self.ctx.device, cast="both")
         E = int(src.shape[0])
         if E > scores.shape[0]:  # NumPy's error for scores[column], as the reference raises it
             raise IndexError(f"index {E - 1} is out of bounds for axis 0 with size "
@@ -590,8 +428,8 @@ class Engine:
         status = np.zeros(max(num_nodes, 1), dtype=np.uint8)
         counts = np.zeros(len(self.SEGK_CLASSES), dtype=np.int64)
         ng, na = ctypes.c_int64(0), ctypes.c_int64(0)
-        self.ctx.call("gs_segment_topk", ptr(scores), GS_HOST, int(scores.shape[0]), ptr(src),
-                      GS_HOST, E, int(num_nodes), int(k), ptr(mask), GS_HOST, ptr(status), GS_HOST,
+        self.ctx.call("gs_segment_topk", ptr(scores), sloc, int(scores.shape[0]), ptr(src),
+                      loc, E, int(num_nodes), int(k), ptr(mask), GS_HOST, ptr(status), GS_HOST,
                       ctypes.byref(ng), ctypes.byref(na), ptr(counts), len(counts))
         info = {"n_guaranteed": ng.value, "n_ambiguous": na.value,
                 "classes": dict(zip(self.SEGK_CLASSES, (int(v) for v in counts)))}
@@ -602,17 +440,7 @@ class Engine:
     # a new LDS tile and the pairwise total a new subtree
     SAMPLE_TILE, SAMPLE_SUBTREE = 1024, 2048
 
-    @staticmethod
-    def _pcg64_words(rng: np.random.Generator):
-        """(state_hi, state_lo, inc_hi, inc_lo) of a Generator(PCG64)."""
-        st = rng.bit_generator.state
-        if st.get("bit_generator") != "PCG64":
-            raise NotImplementedError("the device stream supports the PCG64 bit generator")
-        if st.get("has_uint32"):
-            raise NotImplementedError("PCG64 state with a buffered uint32")
-        s, inc = int(st["state"]["state"]), int(st["state"]["inc"])
-        m64 = (1 << 64) - 1
-        return s >> 64, s & m64, inc >> 64, inc & m64
+    _pcg64_words = staticmethod(A.pcg64_words)
 
     def sample_mask(self, scores: np.ndarray, num_edges: int, num_keep: int,
                     rng: np.random.Generator):
@@ -622,11 +450,11 @@ class Engine:
         Returns ``(mask, status, rounds, draws)``: ``status`` 0 = ``mask`` (bool[E]) was
         written by the device rounds, 1 = degenerate input, NumPy's own call decides
         (``mask`` is None)."""
-        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        scores, sloc = A.inp(scores, np.float64, "scores", self.ctx.device)
         words = self._pcg64_words(rng)
         mask = np.zeros(max(int(num_edges), 1), dtype=np.uint8)
         status, rounds, draws = ctypes.c_int32(1), ctypes.c_int64(0), ctypes.c_int64(0)
-        self.ctx.call("gs_sample_mask", ptr(scores), GS_HOST, int(scores.shape[0]), int(num_edges),
+        self.ctx.call("gs_sample_mask", ptr(scores), sloc, int(scores.shape[0]), int(num_edges),
                       int(num_keep), *words, ptr(mask), GS_HOST, ctypes.byref(status),
                       ctypes.byref(rounds), ctypes.byref(draws))
         if status.value != 0:
@@ -636,34 +464,12 @@ class Engine:
     def pcg64_doubles(self, rng: np.random.Generator, offset: int, n: int, out=None):
         """gs_pcg64_doubles: ``rng.random(offset + n)[offset:]`` drawn on the device
         (into the CUDA float64 tensor ``out`` of >= n elements when given)."""
-        if out is not None:
-            import torch
-
-            self._need(out, n, (torch.float64,), "out")
-            if not out.is_cuda:
-                raise ValueError("out must be a CUDA float64 tensor")
-            self.ctx.call("gs_pcg64_doubles", *self._pcg64_words(rng), int(offset), int(n), ptr(out),
-                          GS_DEVICE)
-            return out
-        out = np.empty(max(n, 1), dtype=np.float64)
-        self.ctx.call("gs_pcg64_doubles", *self._pcg64_words(rng), int(offset), int(n), ptr(out),
-                      GS_HOST)
-        return out[:n]
+        o, loc = A.out(out, np.float64, max(n, 1) if out is None else n, "out", self.ctx.device,
+                       short=IndexError)
+        self.ctx.call("gs_pcg64_doubles", *self._pcg64_words(rng), int(offset), int(n), ptr(o), loc)
+        return o[:n] if out is None else out
 
     # -- symmetric random baseline (gs_undirected_ids / gs_random_mask) ---------
-    @staticmethod
-    def _i64_input(a):
-        """A contiguous int64 numpy array or CUDA tensor, and where it lives."""
-        if isinstance(a, np.ndarray):
-            return np.ascontiguousarray(a, dtype=np.int64), GS_HOST
-        import torch
-
-        if a.dtype != torch.int64:
-            a = a.to(torch.int64)
-        if not a.is_cuda:
-            return np.ascontiguousarray(a.detach().numpy()), GS_HOST
-        return a.contiguous(), GS_DEVICE
-
     def undirected_ids(self, src, dst, num_nodes: int, out=None):
         """gs_undirected_ids: ``np.unique(keys, return_inverse=True)[1]`` of the undirected
         keys ``min * (num_nodes + 1) + max`` (random.py:23-30).  ``src`` / ``dst``: int64
@@ -673,22 +479,9 @@ class Engine:
         Returns ``(inverse, n_undirected, status)``; status 1 = the input is outside the
         device contract, nothing was written (``inverse`` is None) and the reference's own
         NumPy calls decide."""
-        src, loc = self._i64_input(src)
-        dst, dloc = self._i64_input(dst)
-        if loc != dloc:
-            raise ValueError("src and dst must both be numpy arrays or both CUDA tensors")
-        E = int(src.shape[0])
-        if int(dst.shape[0]) != E:
-            raise ValueError(f"src holds {E} ids, dst {int(dst.shape[0])}")
-        if out is None:
-            inv, iloc = np.empty(max(E, 1), dtype=np.int64), GS_HOST
-        else:
-            import torch
-
-            self._need(out, E, (torch.int64,), "out")
-            if not out.is_cuda:
-                raise ValueError("out must be a CUDA int64 tensor of >= E elements")
-            inv, iloc = out, GS_DEVICE
+        src, dst, E, loc = A.pair(src, dst, self.ctx.device)
+        inv, iloc = A.out(out, np.int64, max(E, 1) if out is None else E, "out", self.ctx.device,
+                          short=IndexError)
         cnt, status = ctypes.c_int64(0), ctypes.c_int32(1)
         self.ctx.call("gs_undirected_ids", int(num_nodes), E, ptr(src), ptr(dst), loc, ptr(inv), iloc,
                       ctypes.byref(cnt), ctypes.byref(status))
@@ -704,23 +497,11 @@ class Engine:
 
         Returns ``(mask, cut, beyond, tied)`` as topk_mask does; IndexError when an
         ``inverse`` entry is outside ``[-len(scores), len(scores))``, as NumPy raises."""
-        if isinstance(scores, np.ndarray):
-            scores, sloc = np.ascontiguousarray(scores, dtype=np.float64), GS_HOST
-        elif scores.is_cuda:
-            scores, sloc = scores.contiguous(), GS_DEVICE
-        else:
-            scores, sloc = np.ascontiguousarray(scores.numpy(), dtype=np.float64), GS_HOST
-        if str(scores.dtype) not in ("float64", "torch.float64"):
-            raise TypeError(f"scores must be float64, got {scores.dtype}")
-        inverse, iloc = self._i64_input(inverse)
+        scores, sloc = A.inp(scores, np.float64, "scores", self.ctx.device)
         m, E = int(scores.shape[0]), int(num_edges)
-        self._need(inverse, E, (inverse.dtype,), "inverse")
-        if out is None:
-            mask, mloc = np.zeros(max(E, 1), dtype=np.uint8), GS_HOST
-        else:
-            if not out.is_cuda or out.numel() < E or out.element_size() != 1:
-                raise ValueError("out must be a CUDA uint8/bool tensor of >= num_edges elements")
-            mask, mloc = out, GS_DEVICE
+        inverse, iloc = A.inp(inverse, np.int64, "inverse", self.ctx.device, E, cast="both",
+                              short=IndexError)
+        mask, mloc = A.mask_out(out, E, self.ctx.device)
         cut, nb, nt, bad = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
         self.ctx.call("gs_random_mask", ptr(scores), sloc, m, int(n_keep), ptr(inverse), iloc, E,
                       ptr(mask), mloc, ctypes.byref(cut), ctypes.byref(nb), ctypes.byref(nt),
@@ -744,33 +525,11 @@ class Engine:
         component; a CUDA tensor when the ids are) and ``info`` with ``n_forest``
         (``|F|`` = num_nodes - components), ``n_marked`` (mask bytes set) and ``rounds``.
         ValueError for fewer scores than columns or an id outside ``[0, num_nodes)``."""
-        if isinstance(scores, np.ndarray):
-            scores, sloc = np.ascontiguousarray(scores, dtype=np.float64), GS_HOST
-        elif scores.is_cuda:
-            scores, sloc = scores.contiguous(), GS_DEVICE
-        else:
-            scores, sloc = np.ascontiguousarray(scores.numpy(), dtype=np.float64), GS_HOST
-        if str(scores.dtype) not in ("float64", "torch.float64"):
-            raise TypeError(f"scores must be float64, got {scores.dtype}")
-        src, loc = self._i64_input(src)
-        dst, dloc = self._i64_input(dst)
-        if loc != dloc:
-            raise ValueError("src and dst must both be numpy arrays or both CUDA tensors")
-        E, n = int(src.shape[0]), int(num_nodes)
-        if int(dst.shape[0]) != E:
-            raise ValueError(f"src holds {E} ids, dst {int(dst.shape[0])}")
-        if out is None:
-            mask, mloc = np.zeros(max(E, 1), dtype=np.uint8), GS_HOST
-        else:
-            if not out.is_cuda or out.numel() < E or out.element_size() != 1:
-                raise ValueError("out must be a CUDA uint8/bool tensor of >= E elements")
-            mask, mloc = out, GS_DEVICE
-        if loc == GS_DEVICE:
-            import torch
-
-            labels = torch.empty(max(n, 1), dtype=torch.int32, device=src.device)
-        else:
-            labels = np.empty(max(n, 1), dtype=np.int32)
+        scores, sloc = A.inp(scores, np.float64, "scores", self.ctx.device)
+        src, dst, E, loc = A.pair(src, dst, self.ctx.device)
+        n = int(num_nodes)
+        mask, mloc = A.mask_out(out, E, self.ctx.device)
+        labels = A.alloc(max(n, 1), np.int32, src)
         nf, nm, rounds = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
         self.ctx.call("gs_spanning_forest", ptr(scores), sloc, int(scores.shape[0]), ptr(src), ptr(dst),
                       loc, E, n, int(bool(keep_lowest)), int(bool(expand)), ptr(mask), mloc,
@@ -794,31 +553,11 @@ class Engine:
         written (the arrays are None) and the specification decides on the host."""
         if method not in self.SPECTRAL_METHODS:
             raise ValueError(f"method must be one of {tuple(self.SPECTRAL_METHODS)}, got {method!r}")
-        if isinstance(scores, np.ndarray):
-            scores, sloc = np.ascontiguousarray(scores, dtype=np.float64), GS_HOST
-        elif scores.is_cuda:
-            scores, sloc = scores.contiguous(), GS_DEVICE
-        else:
-            scores, sloc = np.ascontiguousarray(scores.numpy(), dtype=np.float64), GS_HOST
-        if str(scores.dtype) not in ("float64", "torch.float64"):
-            raise TypeError(f"scores must be float64, got {scores.dtype}")
-        src, loc = self._i64_input(src)
-        dst, dloc = self._i64_input(dst)
-        if loc != dloc:
-            raise ValueError("src and dst must both be numpy arrays or both CUDA tensors")
-        E = int(src.shape[0])
-        if int(dst.shape[0]) != E:
-            raise ValueError(f"src holds {E} ids, dst {int(dst.shape[0])}")
+        scores, sloc = A.inp(scores, np.float64, "scores", self.ctx.device)
+        src, dst, E, loc = A.pair(src, dst, self.ctx.device)
         words = self._pcg64_words(rng)
-        if loc == GS_DEVICE:
-            import torch
-
-            new = lambda dt: torch.empty(max(E, 1), dtype=dt, device=src.device)  # noqa: E731
-            mask, weight = new(torch.uint8), new(torch.float64)
-            counts, inverse = new(torch.int64), new(torch.int64)
-        else:
-            mask, weight = np.zeros(max(E, 1), dtype=np.uint8), np.zeros(max(E, 1), dtype=np.float64)
-            counts, inverse = np.zeros(max(E, 1), dtype=np.int64), np.zeros(max(E, 1), dtype=np.int64)
+        mask, weight, counts, inverse = (A.alloc(max(E, 1), dt, src)
+                                         for dt in (np.uint8, np.float64, np.int64, np.int64))
         m, kept, mx, irr, draws = (ctypes.c_int64(0) for _ in range(5))
         status = ctypes.c_int32(1)
         self.ctx.call("gs_spectral_sample", ptr(scores), sloc, int(scores.shape[0]), ptr(src), ptr(dst),
@@ -831,24 +570,22 @@ class Engine:
                 "n_irregular": irr.value, "draws": draws.value}
         if status.value != 0:
             return None, None, None, None, info
-        if loc == GS_DEVICE:
-            return mask[:E].view(torch.bool), weight[:E], counts[:m.value], inverse[:E], info
-        return mask[:E].view(bool), weight[:E], counts[:m.value], inverse[:E], info
+        return A.as_bool(mask[:E]), weight[:E], counts[:m.value], inverse[:E], info
 
     def sample_probs(self, scores: np.ndarray):
         """gs_sample_probs: (probs, total) of sparsify_sampled's normalisation."""
-        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        scores, sloc = A.inp(scores, np.float64, "scores", self.ctx.device)
         p = np.empty(scores.shape[0], dtype=np.float64)
         total = ctypes.c_double(0.0)
-        self.ctx.call("gs_sample_probs", ptr(scores), GS_HOST, int(scores.shape[0]), ptr(p), GS_HOST,
+        self.ctx.call("gs_sample_probs", ptr(scores), sloc, int(scores.shape[0]), ptr(p), GS_HOST,
                       ctypes.byref(total))
         return p, total.value
 
     def cumsum_ordered(self, p: np.ndarray) -> np.ndarray:
         """gs_cumsum_ordered: ``np.cumsum(p)`` (the sequential fp64 add chain)."""
-        p = np.ascontiguousarray(p, dtype=np.float64)
+        p, ploc = A.inp(p, np.float64, "p", self.ctx.device)
         out = np.empty(max(p.shape[0], 1), dtype=np.float64)
-        self.ctx.call("gs_cumsum_ordered", ptr(p), GS_HOST, int(p.shape[0]), ptr(out), GS_HOST)
+        self.ctx.call("gs_cumsum_ordered", ptr(p), ploc, int(p.shape[0]), ptr(out), GS_HOST)
         return out[:p.shape[0]]
 
     def topk_mask(self, scores, num_edges: int, num_keep: int, keep_lowest: bool, out=None):
@@ -856,22 +593,11 @@ class Engine:
         numpy array or a CUDA float64 tensor; ``out``: an optional CUDA uint8/bool
         tensor of >= num_edges elements that receives the mask on the device (then
         returned as is) instead of a host numpy bool array."""
-        if isinstance(scores, np.ndarray):
-            scores = np.ascontiguousarray(scores, dtype=np.float64)
-            sloc = GS_HOST
-        else:
-            sloc = GS_DEVICE if scores.is_cuda else GS_HOST
-            if sloc == GS_HOST:
-                scores = np.ascontiguousarray(scores.numpy(), dtype=np.float64)
+        scores, sloc = A.inp(scores, np.float64, "scores", self.ctx.device)
         nnz = int(scores.shape[0])
-        if out is None:
-            mask, mloc = np.zeros(num_edges, dtype=np.uint8), GS_HOST
-        else:
-            if not out.is_cuda or out.numel() < num_edges or out.element_size() != 1:
-                raise ValueError("out must be a CUDA uint8/bool tensor of >= num_edges elements")
-            mask, mloc = out, GS_DEVICE
+        mask, mloc = A.mask_out(out, num_edges, self.ctx.device)
         cut, nb, nt = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_int64(0)
         self.ctx.call("gs_topk_mask", ptr(scores), sloc, nnz, num_edges, num_keep,
                       int(keep_lowest), ptr(mask), mloc, ctypes.byref(cut), ctypes.byref(nb),
                       ctypes.byref(nt))
-        return (mask.view(bool) if out is None else out), cut.value, nb.value, nt.value
+        return (mask[:num_edges].view(bool) if out is None else out), cut.value, nb.value, nt.value

@@ -37,7 +37,8 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from ._lib import GS_HOST, Context, ptr
+from . import _args as A
+from ._lib import Context, ptr
 from .data import Data
 
 # the dataset names the reference's callers pass (run_ablation.py:46-47,361;
@@ -71,17 +72,15 @@ def coalesce_edges(edge_index, num_nodes: int, undirected: bool = True,
                    remove_self_loops: bool = False, ctx: Context | None = None) -> np.ndarray:
     """Canonical int64 [2, m] edge list (gs_coalesce_edges): with ``undirected``
     every reversed pair is added; sorted by (row, col), duplicates removed."""
+    c = _context(ctx)
     ei = np.asarray(edge_index, dtype=np.int64).reshape(2, -1)
-    E = int(ei.shape[1])
-    src = np.ascontiguousarray(ei[0])
-    dst = np.ascontiguousarray(ei[1])
+    src, dst, E, loc = A.pair(ei[0], ei[1], c.device)
     cap = max(2 * E if undirected else E, 1)
     out_s = np.empty(cap, dtype=np.int64)
     out_d = np.empty(cap, dtype=np.int64)
     m = ctypes.c_int64(cap)
-    _context(ctx).call("gs_coalesce_edges", int(num_nodes), E, ptr(src), ptr(dst),
-                       int(bool(undirected)), int(bool(remove_self_loops)), ptr(out_s), ptr(out_d),
-                       ctypes.byref(m), GS_HOST)
+    c.call("gs_coalesce_edges", int(num_nodes), E, ptr(src), ptr(dst), int(bool(undirected)),
+           int(bool(remove_self_loops)), ptr(out_s), ptr(out_d), ctypes.byref(m), loc)
     return np.stack([out_s[: m.value], out_d[: m.value]])
 
 

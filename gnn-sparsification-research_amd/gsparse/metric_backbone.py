@@ -18,6 +18,7 @@ import numpy as np
 import torch
 from numpy.typing import NDArray
 
+from . import _args as A
 from ._lib import GS_HOST, Context, ptr
 from .data import Data
 
@@ -42,6 +43,22 @@ def check_weights(edge_weights, n_edges: int) -> None:
         raise IndexError(f"index {nw} is out of bounds for axis 0 with size {nw}")
 
 
+def _columns(edge_index, edge_weights, device: int):
+    """(src, dst, w, E, loc): the columns as int64 / int64 / float64 on one side (copies
+    where cast, kept alive by the caller for the run); w is None without weights."""
+    if getattr(edge_index, "ndim", 2) != 2 or len(edge_index) != 2:
+        raise ValueError("edge_index must be [2, E]")
+    src, dst, E, loc = A.pair(edge_index[0], edge_index[1], device)
+    if edge_weights is None:
+        return src, dst, None, E, loc
+    ew = edge_weights if A.is_tensor(edge_weights) else np.asarray(edge_weights)
+    w, wloc = A.inp(ew.reshape(-1)[:E], np.float64, "edge_weights", device, cast="both")
+    check_weights(w, E)
+    if loc != wloc:
+        raise ValueError("edge_index and edge_weights must be on the same side")
+    return src, dst, w, E, loc
+
+
 def backbone_mask(edge_index: np.ndarray, num_nodes: int, edge_weights: np.ndarray,
                   epsilon: float = 1e-9, ctx: Context | None = None,
                   return_relax: bool = False, part: int = 0, nparts: int = 1):
@@ -51,18 +68,12 @@ def backbone_mask(edge_index: np.ndarray, num_nodes: int, edge_weights: np.ndarr
     as the library labels them: graphs without id locality are relabeled by
     degree first) are decided here (the rest read False): the parts OR to the
     whole mask."""
-    ei = np.asarray(edge_index, dtype=np.int64)
-    E = ei.shape[1]
-    src = np.ascontiguousarray(ei[0])
-    dst = np.ascontiguousarray(ei[1])
-    w = np.ascontiguousarray(np.asarray(edge_weights, dtype=np.float64).reshape(-1)[:E])
-    check_weights(w, E)
-    keep = np.zeros(max(E, 1), dtype=np.uint8)
-    relax = ctypes.c_int64(0)
     c = _context(ctx)
+    src, dst, w, E, loc = _columns(np.asarray(edge_index), edge_weights, c.device)
+    keep, kloc = A.mask_out(None, E, c.device)
+    relax = ctypes.c_int64(0)
     c.call("gs_metric_backbone_part", int(num_nodes), E, ptr(src), ptr(dst), ptr(w), len(w),
-           GS_HOST, float(epsilon), int(part), int(nparts), ptr(keep), GS_HOST,
-           ctypes.byref(relax))
+           loc, float(epsilon), int(part), int(nparts), ptr(keep), kloc, ctypes.byref(relax))
     mask = keep[:E].view(bool)
     return (mask, relax.value) if return_relax else mask
 
@@ -82,69 +93,17 @@ class BackboneStages:
         self.ctx = _context(ctx)
         self.n = self.E = self.K = 0
 
-    @staticmethod
-    def _p(a):
-        from ._lib import GS_DEVICE
-
-        if isinstance(a, torch.Tensor):
-            return a.data_ptr(), (GS_DEVICE if a.is_cuda else GS_HOST)
-        return ptr(a), GS_HOST
-
-    def _on_device(self, t: torch.Tensor, what: str) -> None:
-        if t.is_cuda and t.device.index != self.ctx.device:
-            raise ValueError(f"{what} is on {t.device}, the context drives cuda:{self.ctx.device}")
-
-    def _out(self, buf, dtype, count: int, what: str):
-        """An output buffer the library writes `count` elements of `dtype` into."""
-        if isinstance(buf, torch.Tensor):
-            tdt = {np.uint8: torch.uint8, np.float64: torch.float64, np.int32: torch.int32}[dtype]
-            if buf.dtype != tdt:
-                raise TypeError(f"{what} must be {tdt}, got {buf.dtype}")
-            if not buf.is_contiguous():
-                raise ValueError(f"{what} must be contiguous")
-            self._on_device(buf, what)
-            n = buf.numel()
-        else:
-            if not isinstance(buf, np.ndarray) or buf.dtype != dtype or not buf.flags.c_contiguous:
-                raise TypeError(f"{what} must be a contiguous {np.dtype(dtype)} array")
-            n = buf.size
-        if n < count:
-            raise ValueError(f"{what} holds {n} entries, the library writes {count}")
-        return self._p(buf)
-
     def _columns(self, edge_index, edge_weights):
-        """(src, dst, w) as int64 / int64 / float64 on one side, E, and their pointers."""
-        if isinstance(edge_index, torch.Tensor) and edge_index.is_cuda:
-            self._on_device(edge_index, "edge_index")
-            if edge_index.dim() != 2 or edge_index.shape[0] != 2:
-                raise ValueError("edge_index must be [2, E]")
-            src = edge_index[0].to(torch.int64).contiguous()
-            dst = edge_index[1].to(torch.int64).contiguous()
-            E = int(src.numel())
-        else:
-            ei = np.asarray(edge_index.cpu() if isinstance(edge_index, torch.Tensor) else edge_index,
-                            dtype=np.int64)
-            E = ei.shape[1]
-            src, dst = np.ascontiguousarray(ei[0]), np.ascontiguousarray(ei[1])
-        if isinstance(edge_weights, torch.Tensor) and edge_weights.is_cuda:
-            self._on_device(edge_weights, "edge_weights")
-            w = edge_weights.reshape(-1)[:E].to(torch.float64).contiguous()
-        else:
-            ew = edge_weights.cpu() if isinstance(edge_weights, torch.Tensor) else edge_weights
-            w = np.ascontiguousarray(np.asarray(ew, dtype=np.float64).reshape(-1)[:E])
-        check_weights(w, E)
-        (ps, loc), (pd, _), (pw, wloc) = self._p(src), self._p(dst), self._p(w)
-        if loc != wloc:
-            raise ValueError("edge_index and edge_weights must be on the same side")
-        self._keep_alive = (src, dst, w)
-        return E, ps, pd, pw, len(w), loc
+        """E and the arguments (src, dst, w, nw, loc) of the columns, kept alive for the run."""
+        src, dst, w, E, loc = self._keep_alive = _columns(edge_index, edge_weights, self.ctx.device)
+        return E, (ptr(src), ptr(dst), ptr(w), len(w), loc)
 
     def begin(self, edge_index, num_nodes: int, edge_weights, epsilon: float, part: int,
               nparts: int) -> int:
         """Graph, columns by row, landmark searches l = part (mod nparts); returns K."""
-        E, ps, pd, pw, nw, loc = self._columns(edge_index, edge_weights)
+        E, cols = self._columns(edge_index, edge_weights)
         K = ctypes.c_int32(0)
-        self.ctx.call("gs_bb_begin", int(num_nodes), E, ps, pd, pw, nw, loc, float(epsilon),
+        self.ctx.call("gs_bb_begin", int(num_nodes), E, *cols, float(epsilon),
                       int(part), int(nparts), ctypes.byref(K))
         self.n, self.E, self.K = int(num_nodes), E, int(K.value)
         return self.K
@@ -153,22 +112,23 @@ class BackboneStages:
                   nparts: int, keep):
         """gs_metric_backbone_part: keep bytes of the columns (u, v) with max(u, v) %
         nparts == part (ids as the library labels them), 0 elsewhere, into `keep`."""
-        E, ps, pd, pw, nw, loc = self._columns(edge_index, edge_weights)
-        pk, kloc = self._out(keep, np.uint8, max(E, 1), "keep")
+        E, cols = self._columns(edge_index, edge_weights)
+        k, kloc = A.out(keep, np.uint8, max(E, 1), "keep", self.ctx.device)
         relax = ctypes.c_int64(0)
-        self.ctx.call("gs_metric_backbone_part", int(num_nodes), E, ps, pd, pw, nw, loc,
-                      float(epsilon), int(part), int(nparts), pk, kloc, ctypes.byref(relax))
+        self.ctx.call("gs_metric_backbone_part", int(num_nodes), E, *cols,
+                      float(epsilon), int(part), int(nparts), ptr(k), kloc, ctypes.byref(relax))
         self.relax = relax.value
         return keep
 
     def landmarks_io(self, D, complete, out: bool):
         if self.K == 0 or self.E == 0:
             return  # the library copies nothing then
-        pD, loc = self._out(D, np.float64, self.K * self.n, "landmark labels D")
-        pc, cloc = self._out(complete, np.int32, self.K, "landmark completeness flags")
+        D, loc = A.out(D, np.float64, self.K * self.n, "landmark labels D", self.ctx.device)
+        complete, cloc = A.out(complete, np.int32, self.K, "landmark completeness flags",
+                               self.ctx.device)
         if loc != cloc:
             raise ValueError("D and complete must be on the same side")
-        self.ctx.call("gs_bb_landmarks_io", pD, pc, loc, 0 if out else 1)
+        self.ctx.call("gs_bb_landmarks_io", ptr(D), ptr(complete), loc, 0 if out else 1)
 
     def certify(self, part: int, nparts: int):
         self.ctx.call("gs_bb_certify", int(part), int(nparts))
@@ -176,8 +136,8 @@ class BackboneStages:
     def state_io(self, state, out: bool):
         if self.E == 0:
             return
-        p, loc = self._out(state, np.uint8, self.E, "state")
-        self.ctx.call("gs_bb_state_io", p, loc, 0 if out else 1)
+        state, loc = A.out(state, np.uint8, self.E, "state", self.ctx.device)
+        self.ctx.call("gs_bb_state_io", ptr(state), loc, 0 if out else 1)
 
     def plan(self) -> int:
         nb = ctypes.c_int64(0)
@@ -189,11 +149,9 @@ class BackboneStages:
 
     def finish(self, keep=None):
         """Keep bytes of every column (into ``keep`` if given) and the relaxations."""
-        if keep is None:
-            keep = np.zeros(max(self.E, 1), dtype=np.uint8)
-        p, loc = self._out(keep, np.uint8, max(self.E, 1), "keep")
+        keep, loc = A.out(keep, np.uint8, max(self.E, 1), "keep", self.ctx.device, fresh=np.zeros)
         relax = ctypes.c_int64(0)
-        self.ctx.call("gs_bb_finish", p, loc, ctypes.byref(relax))
+        self.ctx.call("gs_bb_finish", ptr(keep), loc, ctypes.byref(relax))
         self._keep_alive = None
         self.relax = relax.value
         return keep, relax.value
@@ -301,20 +259,12 @@ def pair_distances(edge_index: np.ndarray, num_nodes: int, weights, pairs,
     the graph metric_backbone.py:70-79 builds (gs_pair_distances); weights None:
     hop counts."""
     c = _context(ctx)
-    ei = np.asarray(edge_index, dtype=np.int64)
-    src = np.ascontiguousarray(ei[0])
-    dst = np.ascontiguousarray(ei[1])
-    w = None
-    if weights is not None:
-        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1)[: ei.shape[1]])
-        check_weights(w, ei.shape[1])
+    src, dst, w, E, loc = _columns(np.asarray(edge_index), weights, c.device)
     pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    qs = np.ascontiguousarray(pr[:, 0])
-    qt = np.ascontiguousarray(pr[:, 1])
-    out = np.empty(len(pr), dtype=np.float64)
-    c.call("gs_pair_distances", int(num_nodes), int(ei.shape[1]), ptr(src), ptr(dst),
-           ptr(w) if w is not None else None, 0 if w is None else len(w), GS_HOST, int(len(pr)),
-           ptr(qs), ptr(qt), ptr(out))
+    qs, qt, nq, _ = A.pair(pr[:, 0], pr[:, 1], c.device)
+    out = np.empty(nq, dtype=np.float64)
+    c.call("gs_pair_distances", int(num_nodes), E, ptr(src), ptr(dst), ptr(w),
+           0 if w is None else len(w), loc, nq, ptr(qs), ptr(qt), ptr(out))
     return out
 
 

@@ -24,6 +24,7 @@ import os
 
 import numpy as np
 
+from ._args import on_device, to_host
 from .data import Data
 
 # what the last precompute_random_scores / random_sparsify call did: path ("device" or
@@ -97,14 +98,6 @@ def _engine(data: Data, gpu):
         return None
 
 
-def _to_host(a):
-    return a.cpu().numpy() if getattr(a, "is_cuda", False) else a
-
-
-def _on_device(t, eng) -> bool:
-    return getattr(t, "is_cuda", False) and t.device.index == eng.ctx.device
-
-
 def _select_info(path, cut, beyond, tied, n_keep):
     need = n_keep - beyond
     return {"path": path, "cut": cut, "beyond": beyond, "tied": tied, "need": need,
@@ -164,7 +157,7 @@ class RandomBaseline:
         except (TypeError, ValueError):
             return False
         dev = torch.device("cuda", eng.ctx.device)
-        if _on_device(ei, eng):
+        if on_device(ei, eng.ctx.device):
             src, dst = ei[0], ei[1]
         else:
             e = ei.detach().cpu().numpy()
@@ -213,7 +206,7 @@ class RandomBaseline:
             return torch.from_numpy(m).to(ei.device)
         eng = self._eng
         out = None
-        if _on_device(ei, eng):
+        if on_device(ei, eng.ctx.device):
             out = torch.empty(self.num_edges, dtype=torch.bool, device=ei.device)
         m, cut, beyond, tied = eng.random_mask(self._d_scores, self._d_inverse, n_keep,
                                                self.num_edges, out=out)
@@ -294,12 +287,12 @@ def random_sparsify(data: Data, undirected_scores, inverse_idx, retention_ratio:
     s, inv = arrays
     n_keep = max(1, int(len(s) * retention_ratio))
     ei = data.edge_index
-    out = torch.empty(E, dtype=torch.bool, device=ei.device) if _on_device(ei, eng) else None
+    out = torch.empty(E, dtype=torch.bool, device=ei.device) if on_device(ei, eng.ctx.device) else None
     mask, cut, beyond, tied = eng.random_mask(s, inv, n_keep, E, out=out)
     info = _select_info("device", cut, beyond, tied, n_keep)
     if info["ambiguous"] and tb == "numpy":
         _record(dict(info, path="host"))
-        return _host_random_sparsify(data, _to_host(undirected_scores), _to_host(inverse_idx),
+        return _host_random_sparsify(data, to_host(undirected_scores), to_host(inverse_idx),
                                      retention_ratio, device)
     _record(info)
     if isinstance(mask, np.ndarray):
