@@ -211,6 +211,7 @@ void gs_destroy(gs_ctx *c) {
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     if (c->split_abort_ev) (void)hipEventDestroy(c->split_abort_ev);
     if (c->split_abort_host) (void)hipHostFree(c->split_abort_host);
+    if (c->truss_host) (void)hipHostFree(c->truss_host);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }

@@ -182,6 +182,7 @@ struct gs_ctx {
     int64_t split_aborts = 0;              // aborts seen by this context
     std::shared_ptr<gs::BbRun> bb;         // staged metric backbone (gs_bb_*)
     std::shared_ptr<gs::JacState> jac;     // symmetric Jaccard (gs_jac*)
+    void *truss_host = nullptr;            // pinned: the peel's counters as the host reads them (gs_truss.hip)
     gs::DevBuf &buf(const char *name) { return named[name]; }
 };
 

@@ -16,6 +16,7 @@ from .metrics import (
     calculate_effective_resistance_scores,
     calculate_feature_cosine_scores,
     calculate_jaccard_scores,
+    calculate_trussness_scores,
     compute_geodesic_preservation,
     compute_spectral_approximation,
     compute_topology_metrics,
@@ -38,6 +39,7 @@ __all__ = [
     "calculate_effective_resistance_scores",
     "calculate_approx_effective_resistance_scores",
     "calculate_feature_cosine_scores",
+    "calculate_trussness_scores",
     "compute_geodesic_preservation",
     "compute_topology_metrics",
     "compute_topology_preservation",

@@ -129,6 +129,8 @@ SIGNATURES = {
     "gs_spectral_bounds": (_int, [_vp, _vp, _int, _i64, _f64, _i32, _f64, _i32,
                                   ctypes.POINTER(_f64), ctypes.POINTER(_f64),
                                   ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
+    "gs_trussness": (_int, [_vp, _vp, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i32),
+                            ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
 }
 
 

@@ -70,6 +70,8 @@ class GraphSparsifier:
         "degree",
         "feature_cosine",
         "feature-cosine",
+        "truss",
+        "trussness",
     }
 
     _DISTANCE_METRICS = {"effective_resistance", "approx_effective_resistance"}
@@ -100,6 +102,7 @@ class GraphSparsifier:
         self._adj = None
         self._score_cache: Dict[str, np.ndarray] = {}
         self.last_selection: dict = {}
+        self._truss_info: dict = {}  # gs_trussness' counters, kept with the cached scores
 
     # ------------------------------------------------------------------ adj
     @property
@@ -151,6 +154,8 @@ class GraphSparsifier:
             return "degree"
         if metric_lower in {"feature_cosine"}:
             return "feature_cosine"
+        if metric_lower in {"truss", "trussness"}:
+            return "trussness"
         raise ValueError(
             f"Metric '{metric}' not supported. " f"Choose from: {self.SUPPORTED_METRICS}"
         )
@@ -188,6 +193,8 @@ class GraphSparsifier:
                 scores = eng.feature_cosine(x)
             else:
                 scores = eng.feature_cosine(x.detach().cpu().numpy())
+        elif metric_key == "trussness":
+            scores, self._truss_info = eng.trussness()
         else:  # pragma: no cover - unreachable, mirrors core.py:186-188
             raise ValueError(f"Internal error: Unhandled metric '{metric_key}'")
         self._score_cache[metric_key] = scores
@@ -383,6 +390,35 @@ class GraphSparsifier:
         sparse_data.edge_weight = weight[mask].to(torch.float32).to(self.device)
         if return_mask:
             return sparse_data, (mask.cpu(), weight.cpu())
+        return sparse_data
+
+    def sparsify_truss(self, k: int, return_mask: bool = False):
+        """Keep exactly the k-truss (not in the reference): the columns whose trussness
+        (``compute_scores("truss")``, gs_trussness on the device) is ``>= k``, i.e. the
+        largest subgraph in which every edge lies in at least ``k - 2`` triangles.  ``k`` is
+        an integer ``>= 2`` (ValueError otherwise); ``k = 2`` keeps every column but the
+        self-loops, which score 0 and are always dropped.  One score per ``edge_index``
+        column is needed: ValueError when the canonical CSR merged duplicate columns.
+
+        ``last_selection`` records ``path``, ``k``, ``kept``, ``max_truss``, ``levels`` and
+        ``rounds`` (the peel's levels and sub-rounds)."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 2:
+            raise ValueError(f"k must be an integer >= 2, got {k!r}")
+        scores = self.compute_scores("trussness")
+        if len(scores) != self.num_edges:
+            raise ValueError(f"{len(scores)} scores for {self.num_edges} columns: the canonical CSR "
+                             "merged duplicate columns, one score per edge_index column is needed")
+        mask = np.asarray(scores) >= int(k)
+        info = self._truss_info
+        self.last_selection = {"path": "device", "k": int(k), "kept": int(mask.sum()),
+                               "max_truss": info.get("max_truss"), "levels": info.get("levels"),
+                               "rounds": info.get("rounds")}
+        sparse_edge_index = self.data.edge_index[:, torch.from_numpy(mask).to(
+            self.data.edge_index.device)].to(self.device)
+        sparse_data = self.data.clone()
+        sparse_data.edge_index = sparse_edge_index
+        if return_mask:
+            return sparse_data, torch.from_numpy(mask)
         return sparse_data
 
     def spectral_approximation(self, sparse, edge_weight=None, **caps) -> dict:

@@ -283,6 +283,20 @@ class Engine:
         self.ctx.call("gs_common_neighbors", ptr(o), loc)
         return o
 
+    def trussness(self, out=None):
+        """gs_trussness: the trussness of every CSR entry (symmetric graph; exact integers
+        as float64, 0 on diagonal entries) -> ``(scores, info)``, ``info`` holding
+        ``max_truss``, ``levels`` (distinct trussness values), ``rounds`` (sub-rounds of
+        the level-synchronous peel, ``selection.trussness_host``'s layering) and
+        ``host_waits`` (which alone depends on GSPARSE_TRUSS_TAIL)."""
+        o, loc = self._scores_out(self.nnz, out)
+        mx, lv = ctypes.c_int64(0), ctypes.c_int32(0)
+        rd, hw = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.ctx.call("gs_trussness", ptr(o), loc, ctypes.byref(mx), ctypes.byref(lv),
+                      ctypes.byref(rd), ctypes.byref(hw))
+        return o, {"max_truss": mx.value, "levels": lv.value, "rounds": rd.value,
+                   "host_waits": hw.value}
+
     def clustering(self, per_node: bool = False):
         """gs_clustering: nx.average_clustering of the resident (symmetric,
         self-loop-free) graph, bit-identical; optionally the per-node values."""

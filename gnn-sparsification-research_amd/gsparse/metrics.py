@@ -134,6 +134,16 @@ def calculate_feature_cosine_scores(adj: sp.csr_matrix, features: np.ndarray) ->
     return _unpermute(eng.feature_cosine(features), perm)
 
 
+def calculate_trussness_scores(adj: sp.csr_matrix) -> NDArray[np.float64]:
+    """Trussness of every edge (not in the reference): the largest k whose k-truss -- the
+    largest subgraph in which every edge lies in at least k - 2 triangles -- contains it,
+    by the level-synchronous peel on the device (gs_trussness).  Exact integers as float64,
+    0 on stored diagonal entries; the entry values are ignored.  Symmetric adjacency only
+    (NotImplementedError otherwise)."""
+    eng, perm = _engine(adj)
+    return _unpermute(eng.trussness()[0], perm)
+
+
 def compute_geodesic_preservation(
     original_adj: sp.csr_matrix,
     sparse_adj: sp.csr_matrix,

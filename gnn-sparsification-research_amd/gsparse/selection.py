@@ -307,7 +307,52 @@ def connected_mask_device(engine, scores: np.ndarray, edge_index: np.ndarray, nu
     return mask
 
 
-SPECTRAL_METHODS = ("multinomial", "independent")
+def trussness_host(indptr, indices):
+    """The trussness of every entry of a symmetric CSR pattern: the NumPy specification of
+    gs_trussness.  Returns ``(t, levels, rounds)``: ``t`` (int64, one per entry, 0 on the
+    diagonal), the number of levels with a non-empty frontier and their sub-rounds summed.
+
+    On the simple undirected graph of the pattern (diagonal entries take no part): level
+    ``s`` starts at the smallest support among the alive edges; a sub-round gives every
+    alive edge of support ``<= s`` the trussness ``s + 2`` and removes it; the supports
+    are then counted again from scratch (a sparse product per sub-round: obviously right,
+    and slow), and the level goes on while an alive edge has support ``<= s``."""
+    import scipy.sparse as sp
+
+    indptr = np.asarray(indptr, dtype=np.int64)
+    cols = np.asarray(indices, dtype=np.int64)
+    n = len(indptr) - 1
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    keys = rows * n + cols
+    if len(keys) and (np.any(np.diff(keys) <= 0) or not np.array_equal(np.sort(cols * n + rows), keys)):
+        raise ValueError("trussness_host needs a canonical CSR with a symmetric pattern")
+    t = np.zeros(len(cols), dtype=np.int64)
+    alive = rows != cols
+
+    def supports():
+        a = sp.csr_matrix((np.ones(int(alive.sum())), (rows[alive], cols[alive])), shape=(n, n))
+        tri = (a @ a).multiply(a).tocsr()
+        sup = np.zeros(len(cols), dtype=np.int64)
+        sup[alive] = np.asarray(tri[rows[alive], cols[alive]]).ravel().astype(np.int64)
+        return sup
+
+    levels = rounds = 0
+    while alive.any():
+        sup = supports()
+        s = int(sup[alive].min())
+        levels += 1
+        frontier = alive & (sup <= s)
+        while frontier.any():
+            t[frontier] = s + 2
+            alive &= ~frontier
+            rounds += 1
+            if not alive.any():
+                break
+            frontier = alive & (supports() <= s)
+    return t, levels, rounds
+
+
+SPECTRAL_METHODS =("multinomial", "independent")
 
 
 def spectral_sample(scores, edge_index, num_nodes, num_samples, seed=42, method="multinomial"):

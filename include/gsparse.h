@@ -608,6 +608,42 @@ int gs_spectral_bounds(gs_ctx *ctx, const double *hw, int hw_loc, int64_t nhw, d
                        double *lambda_min, double *lambda_max, int32_t *iterations,
                        int64_t *cg_iterations);
 
+/* ---- cohesion: the k-truss decomposition of the resident graph -------------
+ * On the simple undirected graph of the resident CSR pattern (symmetric;
+ * diagonal entries take no part, the multiplicities in data are ignored):
+ * sup(e) is the number of triangles through e, the k-truss is the largest
+ * subgraph in which every edge lies in at least k - 2 triangles of that
+ * subgraph, and the trussness t(e) is the largest k whose k-truss contains e.
+ * Every edge has t >= 2, an edge in no triangle has t = 2, every edge of a
+ * clique K_c that touches nothing else has t = c.
+ *
+ * out[e] (nnz values, out_loc: GS_HOST / GS_DEVICE) is the trussness of CSR
+ * entry e as an exact integer in float64, 0 on diagonal entries, and
+ * out[e] == out[tpos[e]].
+ *
+ * The layering is that of the level-synchronous peel (Kabir and Madduri's PKT).
+ * The supports start as gs_common_neighbors' counts (less the stored diagonal
+ * entries of the two ends).  For s = 0, 1, ...: the frontier is the alive
+ * edges with sup <= s; they get trussness s + 2 and are removed, which takes
+ * one off the support of every alive edge per triangle lost; the alive edges
+ * whose support thereby reaches s form the next frontier of the SAME level (a
+ * sub-round), until that is empty; s then moves to the smallest alive support.
+ * *levels counts the levels with a non-empty frontier (= the distinct
+ * trussness values), *rounds their sub-rounds summed, *max_truss the largest
+ * trussness (0 for a graph with no off-diagonal entry): all three are
+ * properties of the graph, the same on every run, as out is (integer atomics
+ * only).  *host_waits counts the times the call waited on the stream for the
+ * peel (the edge count, once per level, once per sub-round or per chain of
+ * sub-rounds taken by the tail); it depends on GSPARSE_TRUSS_TAIL, read on
+ * every call: a sub-round whose frontier has at most that many edges (default
+ * 16, 0: never), and at most twice as many 64-entry steps over the shorter
+ * neighbour lists of its edges, is run by a single workgroup that goes on with
+ * the level's sub-rounds by itself while the frontier stays within both bounds.
+ * Each counter may be NULL.  GS_EUNSUPPORTED for a directed adjacency or
+ * nnz >= 2^31 - 1; nnz == 0 gives an empty result and zeros. */
+int gs_trussness(gs_ctx *ctx, double *out, int out_loc, int64_t *max_truss,
+                 int32_t *levels, int64_t *rounds, int64_t *host_waits);
+
 #ifdef __cplusplus
 }
 #endif
