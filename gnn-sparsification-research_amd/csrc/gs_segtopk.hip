@@ -7,9 +7,7 @@
 // Otherwise (or with a NaN in the segment) np.argsort's order decides inside the tie
 // block: status 2, no byte set, the caller makes the reference's own call.
 //
-// Segments: count per node (in the range-check pass, which also detects a sorted src),
-// exclusive scan, and -- only for an unsorted src -- a scatter of the column ids
-// (a sorted src is its own grouping: column id = position).  Selection by length:
+// Segments and node lists: gs_seg.hpp.  Selection by length:
 //   d <= k                 every column (handled by the kernel of its length)
 //   d <= 64      SHORT     sub-wave groups of 8 / 16 / 64 lanes, one key per lane; the
 //                          rank is a count of greater / equal keys over the group
@@ -17,110 +15,10 @@
 //                          radix select with an 8-bit LDS histogram per digit
 //   beyond       STREAM    the same select re-reading the keys from HBM per digit
 // Nothing waits for the host before the one copy that returns the counts.
-#include <cstdlib>
-
-#include "gs_internal.hpp"
 #include "gs_keys.hpp"
+#include "gs_seg.hpp"
 
 namespace gs {
-
-static constexpr int kSegkShortMax = 64;     // one key per lane of a wave
-static constexpr int kSegkLdsSmall = 2048;   // 16 KiB of keys: several workgroups per CU
-static constexpr int kSegkLdsMax = 16384;    // 128 KiB of keys: one workgroup per CU
-// node lists by segment length (segments of <= 8 columns are read off the node range)
-enum { SL_16 = 0, SL_64, SL_LDS1, SL_LDS2, SL_STREAM, SL_COUNT };
-
-struct SegkHdr {
-    int bad, unsorted;
-    unsigned long long cls[GS_SEGK_CLASSES];
-    unsigned long long nlist[SL_COUNT];  // nodes per list
-    unsigned long long base[SL_COUNT];   // its start in the shared list array
-    unsigned long long fill[SL_COUNT];   // fill cursors
-    unsigned long long nguar, namb;
-};
-
-__device__ __forceinline__ int segk_class(int64_t d, int64_t k, int smax, int lmax) {
-    if (d <= 0) return GS_SEGK_EMPTY;
-    if (d <= k) return GS_SEGK_ALL;
-    if (d <= smax) return GS_SEGK_SHORT;
-    if (d <= lmax) return GS_SEGK_LDS;
-    return GS_SEGK_STREAM;
-}
-
-// which kernel reads the segment: -1 none (empty, or the 8-lane pass over all nodes)
-__device__ __forceinline__ int segk_list(int64_t d, int smax, int lmax) {
-    if (d <= 0) return -1;
-    if (d <= smax) return d <= 8 ? -1 : d <= 16 ? SL_16 : SL_64;
-    if (d <= lmax) return d <= kSegkLdsSmall ? SL_LDS1 : SL_LDS2;
-    return SL_STREAM;
-}
-
-// range check, sortedness, columns per node -- one read of src
-__global__ void __launch_bounds__(256) k_segk_check(const int64_t *__restrict__ src, int64_t E, int64_t n,
-                                                    SegkHdr *__restrict__ hdr, int64_t *__restrict__ cnt) {
-    int bad = 0, uns = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < E;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t u = src[i];
-        if (u < 0 || u >= n) {
-            bad = 1;
-            continue;
-        }
-        if (i > 0 && src[i - 1] > u) uns = 1;
-        atomicAdd((unsigned long long *)&cnt[u], 1ull);
-    }
-    if (bad) atomicOr(&hdr->bad, 1);
-    if (uns) atomicOr(&hdr->unsorted, 1);
-}
-
-// unsorted src only: column ids grouped by source (any order inside a segment)
-__global__ void __launch_bounds__(256) k_segk_scatter(const int64_t *__restrict__ src, int64_t E,
-                                                      const SegkHdr *__restrict__ hdr,
-                                                      const int64_t *__restrict__ off,
-                                                      int64_t *__restrict__ cur, int64_t *__restrict__ cols) {
-    if (hdr->bad || !hdr->unsorted) return;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < E;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t u = src[i];
-        const int64_t p = off[u] + (int64_t)atomicAdd((unsigned long long *)&cur[u], 1ull);
-        cols[p] = i;
-    }
-}
-
-// fill == 0: nodes per class and per list; fill == 1: the lists
-__global__ void __launch_bounds__(256) k_segk_classify(int64_t n, int64_t k, const int64_t *__restrict__ off,
-                                                       SegkHdr *__restrict__ hdr, int smax, int lmax, int fill,
-                                                       int64_t *__restrict__ list) {
-    if (hdr->bad) return;
-    __shared__ unsigned int sc[GS_SEGK_CLASSES + SL_COUNT];
-    if (threadIdx.x < GS_SEGK_CLASSES + SL_COUNT) sc[threadIdx.x] = 0;
-    __syncthreads();
-    for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < n;
-         u += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t d = off[u + 1] - off[u];
-        const int l = segk_list(d, smax, lmax);
-        if (!fill) {
-            atomicAdd(&sc[segk_class(d, k, smax, lmax)], 1u);
-            if (l >= 0) atomicAdd(&sc[GS_SEGK_CLASSES + l], 1u);
-        } else if (l >= 0) {
-            list[hdr->base[l] + atomicAdd(&hdr->fill[l], 1ull)] = u;
-        }
-    }
-    __syncthreads();
-    if (!fill && threadIdx.x < GS_SEGK_CLASSES + SL_COUNT && sc[threadIdx.x]) {
-        unsigned long long *dst = threadIdx.x < GS_SEGK_CLASSES ? &hdr->cls[threadIdx.x]
-                                                                : &hdr->nlist[threadIdx.x - GS_SEGK_CLASSES];
-        atomicAdd(dst, (unsigned long long)sc[threadIdx.x]);
-    }
-}
-
-__global__ void k_segk_bases(SegkHdr *hdr) {
-    unsigned long long acc = 0;
-    for (int l = 0; l < SL_COUNT; ++l) {
-        hdr->base[l] = acc;
-        acc += hdr->nlist[l];
-    }
-}
 
 // SHORT: W lanes per segment, one key per lane.  LISTED: the segments of list L (their
 // lengths in (W / 2 or 8, W]); else every node of <= min(8, smax) columns.
@@ -300,14 +198,6 @@ __global__ void __launch_bounds__(256) k_segk_tally(int64_t n, int64_t k, const 
     }
 }
 
-// a GSPARSE_SEGK_* knob lowers a class limit (tests reach every class on small graphs)
-static int segk_limit(const char *name, int dflt) {
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    const long v = atol(e);
-    return v < 0 ? 0 : v > dflt ? dflt : (int)v;
-}
-
 }  // namespace gs
 
 using namespace gs;
@@ -335,24 +225,13 @@ extern "C" int gs_segment_topk(gs_ctx *c, const double *scores, int s_loc, int64
                                                          src_loc);
         uint8_t *dm = (uint8_t *)out_device(c, c->buf("segk_mask"), mask, E1, mask_loc);
         uint8_t *dst = (uint8_t *)out_device(c, c->buf("segk_status"), status, n1, status_loc);
-        auto *hdr = (SegkHdr *)c->buf("segk_hdr").ensure(sizeof(SegkHdr));
-        auto *cnt = (int64_t *)c->buf("segk_cnt").ensure(sizeof(int64_t) * (n + 1));
-        auto *off = (int64_t *)c->buf("segk_off").ensure(sizeof(int64_t) * (n + 1));
-        auto *cols = (int64_t *)c->buf("segk_cols").ensure(sizeof(int64_t) * E1);
-        auto *list = (int64_t *)c->buf("segk_list").ensure(sizeof(int64_t) * n1);
         hipEvent_t t0 = prof_begin(c);
-        GS_HIP(hipMemsetAsync(hdr, 0, sizeof(SegkHdr), st));
-        GS_HIP(hipMemsetAsync(cnt, 0, sizeof(int64_t) * (n + 1), st));
         if (E) GS_HIP(hipMemsetAsync(dm, 0, E, st));
         if (n) GS_HIP(hipMemsetAsync(dst, 0, n, st));
-        const unsigned ge = grid_for(E, 256, 8192), gn = grid_for(n, 256, 8192);
-        k_segk_check<<<ge, 256, 0, st>>>(dsrc, E, n, hdr, cnt);
-        exclusive_scan_i64(c, cnt, off, n + 1);
-        GS_HIP(hipMemsetAsync(cnt, 0, sizeof(int64_t) * (n + 1), st));  // now the scatter cursors
-        k_segk_scatter<<<ge, 256, 0, st>>>(dsrc, E, hdr, off, cnt, cols);
-        k_segk_classify<<<gn, 256, 0, st>>>(n, k, off, hdr, smax, lmax, 0, list);
-        k_segk_bases<<<1, 1, 0, st>>>(hdr);
-        k_segk_classify<<<gn, 256, 0, st>>>(n, k, off, hdr, smax, lmax, 1, list);
+        const SegBufs sb = seg_build(c, dsrc, E, n, k, smax, lmax);
+        SegkHdr *hdr = sb.hdr;
+        const int64_t *off = sb.off, *cols = sb.cols, *list = sb.list;
+        const unsigned gn = grid_for(n, 256, 8192);
         // the list lengths stay on the device: fixed grids, workgroups without work leave
         k_segk_short<8, false><<<grid_for(n, 32, 8192), 256, 0, st>>>(ds, off, cols, hdr, list, 0, n, k, smax,
                                                                       dm, dst);

@@ -16,6 +16,7 @@ from .metrics import (
     calculate_effective_resistance_scores,
     calculate_feature_cosine_scores,
     calculate_jaccard_scores,
+    calculate_local_filter_scores,
     calculate_trussness_scores,
     compute_geodesic_preservation,
     compute_spectral_approximation,
@@ -24,7 +25,7 @@ from .metrics import (
     spectral_bounds_dense,
 )
 from .random import RandomBaseline, precompute_random_scores, random_sparsify
-from .selection import spectral_sample
+from .selection import local_filter_scores, local_mask, spectral_sample
 
 __all__ = [
     "GraphSparsifier",
@@ -40,6 +41,7 @@ __all__ = [
     "calculate_approx_effective_resistance_scores",
     "calculate_feature_cosine_scores",
     "calculate_trussness_scores",
+    "calculate_local_filter_scores",
     "compute_geodesic_preservation",
     "compute_topology_metrics",
     "compute_topology_preservation",
@@ -49,4 +51,6 @@ __all__ = [
     "random_sparsify",
     "RandomBaseline",
     "spectral_sample",
+    "local_filter_scores",
+    "local_mask",
 ]

@@ -30,7 +30,7 @@ from .data import Data
 from .engine import Engine
 from .metric_backbone import compute_metric_backbone
 from .selection import (SPECTRAL_METHODS, connected_mask_device, degree_aware_mask_device,
-                        numpy_topk_mask, sampled_mask_device, spectral_mask_device,
+                        local_mask, numpy_topk_mask, sampled_mask_device, spectral_mask_device,
                         spectral_num_samples)
 
 
@@ -103,6 +103,7 @@ class GraphSparsifier:
         self._score_cache: Dict[str, np.ndarray] = {}
         self.last_selection: dict = {}
         self._truss_info: dict = {}  # gs_trussness' counters, kept with the cached scores
+        self._local_info: Dict[str, dict] = {}  # gs_local_scores' counters, by cache key
 
     # ------------------------------------------------------------------ adj
     @property
@@ -413,6 +414,84 @@ class GraphSparsifier:
         self.last_selection = {"path": "device", "k": int(k), "kept": int(mask.sum()),
                                "max_truss": info.get("max_truss"), "levels": info.get("levels"),
                                "rounds": info.get("rounds")}
+        sparse_edge_index = self.data.edge_index[:, torch.from_numpy(mask).to(
+            self.data.edge_index.device)].to(self.device)
+        sparse_data = self.data.clone()
+        sparse_data.edge_index = sparse_edge_index
+        if return_mask:
+            return sparse_data, torch.from_numpy(mask)
+        return sparse_data
+
+    def compute_local_scores(self, metric: str, keep_lowest: bool = False) -> np.ndarray:
+        """The local-filter score of every ``edge_index`` column under ``metric`` (not in
+        the reference; ``selection.local_filter_scores`` is the specification, computed on
+        the device by gs_segment_rank and gs_local_scores, bit for bit): every node ranks
+        its own columns by ``compute_scores(metric)``, and a column scores ``1 - x`` with
+        ``x`` the smallest exponent at which either end keeps it, ``rank + 1 <= d ** x``.
+        Any exponent or retention ratio of ``sparsify_local`` is then a threshold or a
+        top-k over this one array: a sweep costs one ranking.  Cached like the metrics'
+        scores.  One score per ``edge_index`` column is needed: ValueError when the
+        canonical CSR merged duplicate columns."""
+        metric_key = self._normalize_metric_name(metric)
+        key = f"local:{metric_key}:{'lowest' if keep_lowest else 'highest'}"
+        if key in self._score_cache:
+            return self._score_cache[key]
+        scores = self.compute_scores(metric)
+        if len(scores) != self.num_edges:
+            raise ValueError(f"{len(scores)} scores for {self.num_edges} columns: the canonical CSR "
+                             "merged duplicate columns, one score per edge_index column is needed")
+        ei = self.data.edge_index
+        if ei.is_cuda and ei.device.index == self._ctx.device:
+            ids = ei.to(torch.int64)
+        else:
+            ids = ei.detach().cpu().numpy().astype(np.int64, copy=False)
+        local, self._local_info[key] = self._engine.local_scores(
+            scores, ids[0], ids[1], self.num_nodes, keep_lowest, out=np.empty(self.num_edges))
+        self._score_cache[key] = local
+        return local
+
+    def sparsify_local(self, metric: str, exponent: float | None = None,
+                       retention_ratio: float | None = None, keep_lowest: bool = False,
+                       return_mask: bool = False):
+        """Local sparsification (L-Spar, Satuluri et al.; Local Degree / Local Similarity,
+        Hamann et al.; not in the reference): every node keeps its best edges by its own
+        ranking of ``metric``, so sparse regions are not stripped bare as a global cut of a
+        similarity score strips them.  Exactly one of ``exponent`` and ``retention_ratio``
+        is given (ValueError otherwise).
+
+        ``exponent`` in [0, 1]: node ``u`` keeps its ``ceil(d_u ** exponent)`` best columns
+        and a column survives when either end keeps its pair -- ``selection.local_mask`` of
+        ``compute_local_scores``; the kept count is whatever results (1 keeps everything, 0
+        every node's best edge in both directions).  ``retention_ratio`` in (0, 1]: the
+        ``int(E * r)`` highest local scores, the same cut, ``tie_break`` handling and 1.0
+        shortcut as ``sparsify``.
+
+        ``last_selection`` records ``path``, ``mode`` ("exponent" or "ratio"), ``exponent``
+        (None in ratio mode), ``kept``, ``n_top``, ``max_degree`` and ``classes``; in ratio
+        mode also the cut's ``cut`` / ``beyond`` / ``tied``."""
+        if (exponent is None) == (retention_ratio is None):
+            raise ValueError("exactly one of exponent and retention_ratio must be given")
+        if exponent is not None and not 0 <= exponent <= 1:
+            raise ValueError(f"exponent must be in [0, 1], got {exponent}")
+        if retention_ratio is not None and not 0 < retention_ratio <= 1:
+            raise ValueError(f"retention_ratio must be in (0, 1], got {retention_ratio}")
+        if retention_ratio == 1.0:
+            if return_mask:
+                return self.data.clone(), torch.ones(self.num_edges, dtype=torch.bool)
+            return self.data.clone()
+        local = self.compute_local_scores(metric, keep_lowest)
+        metric_key = self._normalize_metric_name(metric)
+        f = self._local_info[f"local:{metric_key}:{'lowest' if keep_lowest else 'highest'}"]
+        if exponent is not None:
+            mask = local_mask(local, exponent)
+            cut = {}
+        else:
+            mask = self._select_mask(local, int(self.num_edges * retention_ratio), False)
+            cut = {k: self.last_selection[k] for k in ("cut", "beyond", "tied")}
+        self.last_selection = {"path": "device", "mode": "exponent" if exponent is not None else "ratio",
+                               "exponent": None if exponent is None else float(exponent),
+                               "kept": int(mask.sum()), "n_top": f["n_top"],
+                               "max_degree": f["max_degree"], "classes": f["classes"], **cut}
         sparse_edge_index = self.data.edge_index[:, torch.from_numpy(mask).to(
             self.data.edge_index.device)].to(self.device)
         sparse_data = self.data.clone()

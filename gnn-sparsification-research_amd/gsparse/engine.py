@@ -449,6 +449,61 @@ class Engine:
                 "classes": dict(zip(self.SEGK_CLASSES, (int(v) for v in counts)))}
         return mask[:E].view(bool), status[:num_nodes], info
 
+    # -- local sparsification (gs_segment_rank / gs_local_scores) ---------------
+    SEGR_CLASSES = ("empty", "short", "lds", "stream")
+
+    def _segment_rank(self, scores, src, n: int, keep_lowest: bool):
+        """``src`` as ``_args.inp`` returned it -> ``(rank, deg, info)`` where ``src`` lives."""
+        scores, sloc = A.inp(scores, np.float64, "scores", self.ctx.device)
+        E = int(src.shape[0])
+        loc = GS_DEVICE if A.on_device(src, self.ctx.device) else GS_HOST
+        rank = A.alloc(max(E, 1), np.int32, src)
+        deg = A.alloc(max(n, 1), np.int64, src)
+        counts = np.zeros(len(self.SEGR_CLASSES), dtype=np.int64)
+        mx = ctypes.c_int64(0)
+        self.ctx.call("gs_segment_rank", ptr(scores), sloc, int(scores.shape[0]), ptr(src), loc, E, n,
+                      int(bool(keep_lowest)), ptr(rank), loc, ptr(deg), loc, ctypes.byref(mx),
+                      ptr(counts), len(counts))
+        info = {"max_degree": mx.value,
+                "classes": dict(zip(self.SEGR_CLASSES, (int(v) for v in counts)))}
+        return rank[:E], deg[:max(n, 0)], info
+
+    def segment_rank(self, scores, src, num_nodes: int, keep_lowest: bool = False):
+        """gs_segment_rank: for every column its rank inside its source node's segment,
+        the number of columns of that node that are better in the strict total order
+        ``(key(score), index)`` larger -- ``keep_lowest``: smaller -- of
+        ``spanning_forest``; 0 is the node's best edge.  ``scores`` (float64, one per
+        column) and ``src`` (int64): numpy arrays or CUDA tensors.
+
+        Returns ``(rank, deg, info)``: ``rank`` (int32 per column) and ``deg`` (int64 per
+        node, its columns) live where ``src`` does; ``info`` holds ``max_degree`` and
+        ``classes`` (nodes per kernel class, keyed by SEGR_CLASSES).  ValueError for fewer
+        scores than columns or a source outside ``[0, num_nodes)``."""
+        src, _ = A.inp(src, np.int64, "src", self.ctx.device, cast="both")
+        return self._segment_rank(scores, src, int(num_nodes), keep_lowest)
+
+    def local_scores(self, scores, src, dst, num_nodes: int, keep_lowest: bool = False, out=None):
+        """The local-filter score of every column (``selection.local_filter_scores`` on
+        the device, bit for bit): gs_segment_rank, the table ``log(max(j, 1))`` for ``j``
+        up to the largest degree by NumPy, gs_local_scores.  ``scores`` (float64, one per
+        column) and ``src`` / ``dst`` (int64): numpy arrays or CUDA tensors; ``out``: an
+        optional float64 array or CUDA tensor of >= E elements that receives the scores.
+
+        Returns ``(local, info)``: ``local`` lives where the ids do (or is ``out``);
+        ``info`` holds ``max_degree``, ``n_top`` (columns scoring 1.0: some end's best
+        edge) and ``classes``."""
+        src, dst, E, loc = A.pair(src, dst, self.ctx.device)
+        n = int(num_nodes)
+        o, oloc = (A.alloc(max(E, 1), np.float64, src), loc) if out is None else \
+            A.out(out, np.float64, E, "out", self.ctx.device)
+        rank, deg, info = self._segment_rank(scores, src, n, keep_lowest)
+        table = np.log(np.maximum(np.arange(max(info["max_degree"], 1) + 1), 1).astype(np.float64))
+        top = ctypes.c_int64(0)
+        self.ctx.call("gs_local_scores", ptr(rank), loc, ptr(src), ptr(dst), loc, E, n, ptr(deg), loc,
+                      ptr(table), GS_HOST, len(table), ptr(o), oloc, ctypes.byref(top))
+        info = {"max_degree": info["max_degree"], "n_top": top.value, "classes": info["classes"]}
+        return (o[:E] if out is None else out), info
+
     # -- score-proportional sampling (gs_sample_*, include/gsparse.h) ----------
     # GS_SAMPLE_TILE / GS_SAMPLE_SUBTREE: the sizes at which the ordered cumsum starts
     # a new LDS tile and the pairwise total a new subtree

@@ -144,6 +144,28 @@ def calculate_trussness_scores(adj: sp.csr_matrix) -> NDArray[np.float64]:
     return _unpermute(eng.trussness()[0], perm)
 
 
+def calculate_local_filter_scores(adj: sp.csr_matrix, scores: np.ndarray,
+                                  keep_lowest: bool = False) -> NDArray[np.float64]:
+    """Local-filter score of every entry under ``scores`` (not in the reference;
+    ``selection.local_filter_scores`` with the entries as the columns, on the device by
+    gs_segment_rank and gs_local_scores): every row ranks its own entries by ``scores`` (one
+    per entry, in storage order; ``keep_lowest``: the lowest first), and an entry scores
+    ``1 - x`` with ``x`` the smallest exponent at which either end of its pair keeps it,
+    ``rank + 1 <= d ** x``.  ``scores >= 1 - e`` is the local sparsifier (L-Spar, Local
+    Degree) at exponent ``e``.  Returned in storage order; ties between equal scores are
+    broken by the canonical (row-major, sorted) position."""
+    eng, perm = _engine(adj)
+    scores = np.asarray(scores, dtype=np.float64)
+    if scores.shape != (eng.nnz,):
+        raise ValueError(f"{scores.shape} scores for {eng.nnz} entries")
+    if perm is not None:
+        scores = scores[perm]
+    indptr, indices, _ = eng.ctx.csr()
+    rows = np.repeat(np.arange(eng.n, dtype=np.int64), np.diff(indptr))
+    local, _ = eng.local_scores(scores, rows, indices.astype(np.int64), eng.n, keep_lowest)
+    return _unpermute(local, perm)
+
+
 def compute_geodesic_preservation(
     original_adj: sp.csr_matrix,
     sparse_adj: sp.csr_matrix,

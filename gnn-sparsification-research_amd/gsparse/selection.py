@@ -352,6 +352,86 @@ def trussness_host(indptr, indices):
     return t, levels, rounds
 
 
+def local_filter_scores(scores, edge_index, num_nodes: int, keep_lowest: bool = False):
+    """The local-filter score of every ``edge_index`` column: the NumPy specification of
+    gs_segment_rank and gs_local_scores (L-Spar, Satuluri et al.; Local Degree / Local
+    Similarity, Hamann et al.; NetworKit's local filter on top of any edge score).
+
+    The segment of node ``u`` is the set of columns with ``src == u``, ``d_u`` its length
+    (loops and duplicate columns are ordinary columns).  Column i is better than column j
+    when ``(score, index)`` is lexicographically larger (``keep_lowest``: smaller), -0.0
+    == +0.0, NaN the largest: ``connected_mask``'s strict total order.  ``rank[i]`` = the
+    better columns of i's own segment.  ``x[i]`` = 0 for rank 0, else ``T[rank + 1] /
+    T[d_src]`` with ``T = log(max(arange(max_deg + 1), 1))``: node ``u`` keeps column i at
+    exponent ``e``, ``rank + 1 <= d_u ** e``, exactly when ``x[i] <= e``.  ``y`` = the
+    minimum of ``x`` over the columns of an unordered pair, ``local = 1 - y`` in [0, 1];
+    1.0 is some end's best edge.
+
+    Returns ``(local, rank, info)``, ``info`` holding ``max_degree`` and ``n_top`` (columns
+    with ``local == 1.0``).  ValueError for fewer scores than columns or an id outside
+    ``[0, num_nodes)``."""
+    ei = np.asarray(edge_index)
+    src, dst = ei[0].astype(np.int64), ei[1].astype(np.int64)
+    E = len(src)
+    if len(scores) < E:
+        raise ValueError(f"{len(scores)} scores for {E} columns: the canonical CSR "
+                         "merged duplicate columns, one score per edge_index column is needed")
+    if E and (min(src.min(), dst.min()) < 0 or max(src.max(), dst.max()) >= num_nodes):
+        raise ValueError(f"edge_index id out of range [0, {num_nodes})")
+    s = np.asarray(scores, dtype=np.float64)[:E]
+    order = np.lexsort((np.arange(E), np.where(s == 0, 0.0, s)))  # ascending (score, index), NaN last
+    if not keep_lowest:
+        order = order[::-1]  # best first
+    by = order[np.argsort(src[order], kind="stable")]
+    deg = np.bincount(src, minlength=num_nodes)
+    off = np.concatenate([[0], np.cumsum(deg)])
+    rank = np.empty(E, dtype=np.int64)
+    rank[by] = np.arange(E) - off[src[by]]
+    max_deg = int(deg.max()) if E else 0
+    table = np.log(np.maximum(np.arange(max(max_deg, 1) + 1), 1).astype(np.float64))
+    x = np.zeros(E)
+    nz = rank > 0
+    x[nz] = table[rank[nz] + 1] / table[deg[src][nz]]
+    inv = np.unique(np.minimum(src, dst) * (num_nodes + 1) + np.maximum(src, dst),
+                    return_inverse=True)[1].reshape(-1)
+    y = np.full(int(inv.max()) + 1 if E else 0, np.inf)
+    np.minimum.at(y, inv, x)
+    local = 1.0 - y[inv]
+    return local, rank, {"max_degree": max_deg, "n_top": int((local == 1.0).sum())}
+
+
+def local_mask(local, exponent: float):
+    """The local sparsifier's mask at ``exponent`` in [0, 1]: ``local >= 1.0 - exponent``
+    (that expression is the definition).  Every node keeps its ``ceil(d ** exponent)`` best
+    columns and a column survives when either end keeps its pair: 1 keeps everything, 0
+    every node's best edge in both directions."""
+    if not 0 <= exponent <= 1:
+        raise ValueError(f"exponent must be in [0, 1], got {exponent}")
+    return local >= 1.0 - exponent
+
+
+def local_mask_device(engine, scores, edge_index, num_nodes: int, exponent: float,
+                      keep_lowest: bool = False, info: dict | None = None):
+    """``local_mask(local_filter_scores(...)[0], exponent)`` on the MI355X
+    (Engine.local_scores); the same mask.  ``edge_index``: a numpy array or a CUDA tensor
+    (the mask then is one too).
+
+    ``info`` (optional dict) receives ``path`` ("device"), ``exponent``, ``kept``,
+    ``n_top``, ``max_degree`` and ``classes``."""
+    if info is None:
+        info = {}
+    if not 0 <= exponent <= 1:
+        raise ValueError(f"exponent must be in [0, 1], got {exponent}")
+    if len(scores) < edge_index.shape[1]:
+        raise ValueError(f"{len(scores)} scores for {edge_index.shape[1]} columns: the canonical CSR "
+                         "merged duplicate columns, one score per edge_index column is needed")
+    local, f = engine.local_scores(scores, edge_index[0], edge_index[1], num_nodes, keep_lowest)
+    mask = local_mask(local, exponent)
+    info.update(path="device", exponent=float(exponent), kept=int(mask.sum()), n_top=f["n_top"],
+                max_degree=f["max_degree"], classes=f["classes"])
+    return mask
+
+
 SPECTRAL_METHODS =("multinomial", "independent")
 
 

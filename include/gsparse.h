@@ -644,6 +644,48 @@ int gs_spectral_bounds(gs_ctx *ctx, const double *hw, int hw_loc, int64_t nhw, d
 int gs_trussness(gs_ctx *ctx, double *out, int out_loc, int64_t *max_truss,
                  int32_t *levels, int64_t *rounds, int64_t *host_waits);
 
+/* ---- local sparsification: segment ranks and the local-filter score ----------
+ * (L-Spar, Satuluri et al. SIGMOD'11; Local Degree / Local Similarity, Hamann et
+ * al.; NetworKit's local filter.  Not in the reference; the NumPy specification
+ * is gsparse/selection.py: local_filter_scores.)
+ * The columns are the E columns of edge_index, scores[i] belongs to column i
+ * (nscores >= E).  The segment of node u is the set of columns with src == u,
+ * d_u its length; loops and duplicate columns are ordinary columns.  Column i is
+ * better than column j when (key(score), index) is lexicographically larger --
+ * keep_lowest: smaller -- with gs_topk_mask's keys (-0.0 == +0.0, NaN the
+ * largest): gs_spanning_forest's strict total order.
+ * gs_segment_rank: rank[i] (int32) = the better columns of i's own segment, 0 =
+ * the node's best edge; deg[u] (int64[n], may be NULL) = d_u; *max_deg = the
+ * largest d_u.  class_counts[0..ncounts): nodes per GS_SEGR_* class, by segment
+ * length: SHORT (<= 64) one column per lane of a sub-wave group and a count of
+ * the better ones, LDS (<= 8192) one workgroup ordering the staged keys in LDS,
+ * STREAM radix sorts of the hubs' columns.  GSPARSE_SEGR_SHORT_MAX / _LDS_MAX
+ * lower the limits, GSPARSE_SEGR_MODE=sort takes every segment through the
+ * STREAM class; all three are read on every call and change class_counts only.
+ * Ties are broken by the column index itself: the same bytes on every run, for a
+ * sorted and an unsorted src.  One wait for the host.  GS_EINVAL for nscores <
+ * E, a src outside [0, n) or n < 1; GS_EUNSUPPORTED for E >= 2^31.
+ * gs_local_scores: the local-filter score of every column from those ranks.
+ * x[i] = 0 for rank[i] == 0, else table[rank[i] + 1] / table[deg[src[i]]] -- one
+ * IEEE divide; table[j] = log(max(j, 1)), j < ntable, computed by the caller
+ * (NumPy's log: the device calls none), so node u keeps column i at exponent e,
+ * rank + 1 <= d_u^e, exactly when x[i] <= e.  y = the minimum of x over the
+ * columns of the unordered pair {src, dst} (gs_undirected_ids; an integer
+ * atomicMin on the bit patterns: exact and run-independent), out[i] = 1 - y: a
+ * value in [0, 1], 1 = some end's best edge, and out >= 1 - e is the mask of the
+ * local sparsifier at exponent e.  *n_top = columns with out == 1.  GS_EINVAL for
+ * ntable <= the degree of a column's source, a rank outside [0, d), an id outside
+ * [0, n) or n < 1; GS_EUNSUPPORTED for n >= 2^31.  E == 0 writes nothing. */
+enum { GS_SEGR_EMPTY = 0, GS_SEGR_SHORT, GS_SEGR_LDS, GS_SEGR_STREAM, GS_SEGR_CLASSES };
+int gs_segment_rank(gs_ctx *ctx, const double *scores, int s_loc, int64_t nscores,
+                    const int64_t *src, int src_loc, int64_t E, int64_t n, int keep_lowest,
+                    int32_t *rank, int rank_loc, int64_t *deg, int deg_loc, int64_t *max_deg,
+                    int64_t *class_counts, int ncounts);
+int gs_local_scores(gs_ctx *ctx, const int32_t *rank, int r_loc, const int64_t *src,
+                    const int64_t *dst, int e_loc, int64_t E, int64_t n, const int64_t *deg,
+                    int d_loc, const double *table, int t_loc, int64_t ntable, double *out,
+                    int out_loc, int64_t *n_top);
+
 #ifdef __cplusplus
 }
 #endif
