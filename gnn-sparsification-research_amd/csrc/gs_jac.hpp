@@ -255,6 +255,16 @@ inline JacState &jac_state(gs_ctx *c) {
 // cc != nullptr: the part's raw counts into its compact owner-entry array
 void jaccard_symmetric(gs_ctx *c, const JacKnobs &k, double *out, int part, int nparts,
                        int counts = 0, uint32_t *cc = nullptr);
+// The triangle counts of the simple undirected graph of the pattern, as the trussness and
+// the Simmelian backbone start from them: the owner-side intersection kernels in count
+// mode (gs_common_neighbors) into device out[nnz] ...
+inline void support_pass(gs_ctx *c, double *out) { jaccard_symmetric(c, jac_knobs(), out, 0, 1, 1); }
+// ... less the stored diagonal entries of the two ends of an off-diagonal entry (r, c),
+// which that count includes: u (v) itself is a "common neighbour" of (u, v) when (u, u)
+// ((v, v)) is stored
+__host__ __device__ __forceinline__ int support_less_diag(double cnt, uint8_t diag_r, uint8_t diag_c) {
+    return (int)cnt - (int)diag_r - (int)diag_c;
+}
 // gs_jac_plan.hip: the kept plan of rows [r0, r1), or a new one; sum of squared degrees
 const JacPlan &jac_plan(gs_ctx *c, const JacKnobs &k, int64_t r0, int64_t r1);
 double jac_deg2(gs_ctx *c);

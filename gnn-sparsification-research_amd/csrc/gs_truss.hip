@@ -125,7 +125,7 @@ __global__ void k_truss_init(const int32_t *__restrict__ rows, const int32_t *__
         const int32_t id = (int32_t)rank[e];
         eu[id] = r;
         ev[id] = c;
-        sup[id] = (int)cnt[e] - (int)diag[r] - (int)diag[c];
+        sup[id] = support_less_diag(cnt[e], diag[r], diag[c]);
         eid[e] = id;
         eid[tpos[e]] = id;
     }
@@ -486,7 +486,7 @@ extern "C" int gs_trussness(gs_ctx *c, double *out, int loc, int64_t *max_truss,
         double *dout = (double *)out_device(c, c->outbuf, out, sizeof(double) * (g.nnz ? g.nnz : 1), loc);
         TrussOut o;
         if (g.nnz) {
-            jaccard_symmetric(c, jac_knobs(), dout, 0, 1, 1);
+            support_pass(c, dout);
             o = truss_run(c, dout);
         }
         finish_out(c, out, dout, sizeof(double) * g.nnz, loc);

@@ -17,6 +17,7 @@ from .metrics import (
     calculate_feature_cosine_scores,
     calculate_jaccard_scores,
     calculate_local_filter_scores,
+    calculate_simmelian_scores,
     calculate_trussness_scores,
     compute_geodesic_preservation,
     compute_spectral_approximation,
@@ -41,6 +42,7 @@ __all__ = [
     "calculate_approx_effective_resistance_scores",
     "calculate_feature_cosine_scores",
     "calculate_trussness_scores",
+    "calculate_simmelian_scores",
     "calculate_local_filter_scores",
     "compute_geodesic_preservation",
     "compute_topology_metrics",

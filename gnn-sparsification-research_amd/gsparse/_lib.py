@@ -131,6 +131,7 @@ SIGNATURES = {
                                   ctypes.POINTER(_i32), ctypes.POINTER(_i64)]),
     "gs_trussness": (_int, [_vp, _vp, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i32),
                             ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "gs_simmelian": (_int, [_vp, _vp, _int, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp, _int]),
     "gs_segment_rank": (_int, [_vp, _vp, _int, _i64, _vp, _int, _i64, _i64, _int, _vp, _int, _vp, _int,
                                ctypes.POINTER(_i64), _vp, _int]),
     "gs_local_scores": (_int, [_vp, _vp, _int, _vp, _vp, _int, _i64, _i64, _vp, _int, _vp, _int, _i64,

@@ -72,6 +72,8 @@ class GraphSparsifier:
         "feature-cosine",
         "truss",
         "trussness",
+        "simmelian",
+        "simmelian_jaccard",
     }
 
     _DISTANCE_METRICS = {"effective_resistance", "approx_effective_resistance"}
@@ -103,6 +105,7 @@ class GraphSparsifier:
         self._score_cache: Dict[str, np.ndarray] = {}
         self.last_selection: dict = {}
         self._truss_info: dict = {}  # gs_trussness' counters, kept with the cached scores
+        self._simmelian_info: dict = {}  # gs_simmelian's counters of the cached score
         self._local_info: Dict[str, dict] = {}  # gs_local_scores' counters, by cache key
 
     # ------------------------------------------------------------------ adj
@@ -157,6 +160,8 @@ class GraphSparsifier:
             return "feature_cosine"
         if metric_lower in {"truss", "trussness"}:
             return "trussness"
+        if metric_lower in {"simmelian", "simmelian_jaccard"}:
+            return "simmelian"
         raise ValueError(
             f"Metric '{metric}' not supported. " f"Choose from: {self.SUPPORTED_METRICS}"
         )
@@ -196,6 +201,8 @@ class GraphSparsifier:
                 scores = eng.feature_cosine(x.detach().cpu().numpy())
         elif metric_key == "trussness":
             scores, self._truss_info = eng.trussness()
+        elif metric_key == "simmelian":
+            scores, self._simmelian_info = eng.simmelian(0)
         else:  # pragma: no cover - unreachable, mirrors core.py:186-188
             raise ValueError(f"Internal error: Unhandled metric '{metric_key}'")
         self._score_cache[metric_key] = scores
@@ -414,6 +421,77 @@ class GraphSparsifier:
         self.last_selection = {"path": "device", "k": int(k), "kept": int(mask.sum()),
                                "max_truss": info.get("max_truss"), "levels": info.get("levels"),
                                "rounds": info.get("rounds")}
+        sparse_edge_index = self.data.edge_index[:, torch.from_numpy(mask).to(
+            self.data.edge_index.device)].to(self.device)
+        sparse_data = self.data.clone()
+        sparse_data.edge_index = sparse_edge_index
+        if return_mask:
+            return sparse_data, torch.from_numpy(mask)
+        return sparse_data
+
+    def simmelian_overlap(self, max_rank: int) -> np.ndarray:
+        """The parametric Simmelian overlap of every CSR entry (not in the reference;
+        ``selection.simmelian_host(..., max_rank)`` on the device, gs_simmelian): the number
+        of neighbours that both ends of the edge rank below ``max_rank`` by the triangles
+        through the tie, ties sharing a rank.  ``max_rank`` is an integer ``>= 1``
+        (ValueError otherwise).  Cached per rank."""
+        if isinstance(max_rank, bool) or not isinstance(max_rank, (int, np.integer)) or max_rank < 1:
+            raise ValueError(f"max_rank must be an integer >= 1, got {max_rank!r}")
+        key = f"simmelian_overlap:{int(max_rank)}"
+        if key not in self._score_cache:
+            self._score_cache[key], info = self._engine.simmelian(int(max_rank))
+            self._simmelian_info = self._simmelian_info or info
+        return self._score_cache[key]
+
+    def sparsify_simmelian(self, retention_ratio: float | None = None, threshold: float | None = None,
+                           max_rank: int | None = None, min_overlap: int | None = None,
+                           return_mask: bool = False):
+        """The Simmelian backbone (Nick et al., ASONAM 2013; NetworKit's Simmelian
+        sparsifiers; not in the reference): an edge is kept when its two ends agree on who
+        their strongest ties are -- the sparsifier that separates communities in dense,
+        noisy graphs.  Exactly one mode is given (ValueError otherwise):
+
+        ``retention_ratio`` in (0, 1]: the ``int(E * r)`` highest non-parametric scores
+        (``compute_scores("simmelian")``), the same cut, ``tie_break`` handling and 1.0
+        shortcut as ``sparsify``.  ``threshold``: the columns with score ``>= threshold``.
+        ``max_rank`` with ``min_overlap`` (integers ``>= 1``): the columns whose ends share
+        at least ``min_overlap`` of their neighbours of rank below ``max_rank``
+        (``simmelian_overlap``), NetworKit's parametric form.
+
+        One score per ``edge_index`` column is needed: ValueError when the canonical CSR
+        merged duplicate columns.  ``last_selection`` records ``path``, ``mode`` ("ratio",
+        "threshold" or "overlap"), ``kept``, ``max_common`` and ``classes``."""
+        modes = (retention_ratio is not None, threshold is not None,
+                 max_rank is not None or min_overlap is not None)
+        if sum(modes) != 1:
+            raise ValueError("give exactly one of retention_ratio, threshold, and max_rank with min_overlap")
+        if modes[0] and not 0 < retention_ratio <= 1:
+            raise ValueError(f"retention_ratio must be in (0, 1], got {retention_ratio}")
+        if modes[1] and not (isinstance(threshold, (int, float, np.integer, np.floating))
+                             and not isinstance(threshold, bool) and threshold == threshold):
+            raise ValueError(f"threshold must be a number, got {threshold!r}")
+        if modes[2]:
+            for name, v in (("max_rank", max_rank), ("min_overlap", min_overlap)):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                    raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        if retention_ratio == 1.0:
+            if return_mask:
+                return self.data.clone(), torch.ones(self.num_edges, dtype=torch.bool)
+            return self.data.clone()
+        scores = self.simmelian_overlap(max_rank) if modes[2] else self.compute_scores("simmelian")
+        if len(scores) != self.num_edges:
+            raise ValueError(f"{len(scores)} scores for {self.num_edges} columns: the canonical CSR "
+                             "merged duplicate columns, one score per edge_index column is needed")
+        if modes[0]:
+            mask = self._select_mask(scores, int(self.num_edges * retention_ratio), False)
+        elif modes[1]:
+            mask = np.asarray(scores) >= threshold
+        else:
+            mask = np.asarray(scores) >= int(min_overlap)
+        info = self._simmelian_info
+        self.last_selection = {"path": "device", "mode": ("ratio", "threshold", "overlap")[modes.index(True)],
+                               "kept": int(mask.sum()), "max_common": info.get("max_common"),
+                               "classes": info.get("classes")}
         sparse_edge_index = self.data.edge_index[:, torch.from_numpy(mask).to(
             self.data.edge_index.device)].to(self.device)
         sparse_data = self.data.clone()

@@ -297,6 +297,26 @@ class Engine:
         return o, {"max_truss": mx.value, "levels": lv.value, "rounds": rd.value,
                    "host_waits": hw.value}
 
+    # gs_simmelian's pair classes (GS_SIM_*), by the shorter of a pair's neighbour lists
+    SIM_CLASSES = ("wave", "mid", "lds", "stream")
+
+    def simmelian(self, max_rank: int = 0, out=None):
+        """gs_simmelian: the Simmelian backbone score of every CSR entry (symmetric graph;
+        ``selection.simmelian_host`` on the device, bit for bit) -> ``(scores, info)``.
+        ``max_rank = 0``: the largest Jaccard ratio of the two ends' ranked neighbourhoods
+        over every rank bound; ``max_rank = k0 >= 1``: their overlap at ``k0``, an exact
+        integer as float64 (ValueError for a negative ``max_rank``).  0 on diagonal
+        entries.  ``info`` holds ``max_common`` (the most common neighbours of a pair),
+        ``nonzero_pairs`` and ``classes`` (pairs per kernel class, keyed by SIM_CLASSES;
+        they alone depend on GSPARSE_SIM_WAVE_MAX / _MID_MAX / _LDS_MAX)."""
+        o, loc = self._scores_out(self.nnz, out)
+        mc, nzp = ctypes.c_int64(0), ctypes.c_int64(0)
+        counts = np.zeros(len(self.SIM_CLASSES), dtype=np.int64)
+        self.ctx.call("gs_simmelian", ptr(o), loc, int(max_rank), ctypes.byref(mc), ctypes.byref(nzp),
+                      ptr(counts), len(counts))
+        return o, {"max_common": mc.value, "nonzero_pairs": nzp.value,
+                   "classes": dict(zip(self.SIM_CLASSES, (int(v) for v in counts)))}
+
     def clustering(self, per_node: bool = False):
         """gs_clustering: nx.average_clustering of the resident (symmetric,
         self-loop-free) graph, bit-identical; optionally the per-node values."""

@@ -144,6 +144,18 @@ def calculate_trussness_scores(adj: sp.csr_matrix) -> NDArray[np.float64]:
     return _unpermute(eng.trussness()[0], perm)
 
 
+def calculate_simmelian_scores(adj: sp.csr_matrix, max_rank: int = 0) -> NDArray[np.float64]:
+    """Simmelian backbone score of every edge (not in the reference; Nick et al., ASONAM
+    2013): every node ranks its neighbours by the triangles through the tie, ties sharing
+    a rank, and an edge scores by the overlap of its two ends' top-ranked neighbourhoods
+    -- the largest Jaccard ratio over every rank bound (``max_rank = 0``), or the overlap
+    at ``max_rank >= 1`` (gs_simmelian; ``selection.simmelian_host`` bit for bit).  0 on
+    stored diagonal entries; the entry values are ignored.  Symmetric adjacency only
+    (NotImplementedError otherwise)."""
+    eng, perm = _engine(adj)
+    return _unpermute(eng.simmelian(max_rank)[0], perm)
+
+
 def calculate_local_filter_scores(adj: sp.csr_matrix, scores: np.ndarray,
                                   keep_lowest: bool = False) -> NDArray[np.float64]:
     """Local-filter score of every entry under ``scores`` (not in the reference;

@@ -352,6 +352,198 @@ def trussness_host(indptr, indices):
     return t, levels, rounds
 
 
+def simmelian_prepare(indptr, indices):
+    """What both modes of ``simmelian_host`` share, a function of the graph alone: the
+    triangle count ``t`` of every entry (-1 on the diagonal), every row's counts in
+    descending order, the tie-aware rank of every entry in its whole row, and the list of
+    (pair, common neighbour) hits with the common neighbour's rank at either end, the
+    other end removed.  Pass it to ``simmelian_host(..., prep=)`` to evaluate several
+    ``max_rank`` on one graph."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    cols = np.asarray(indices, dtype=np.int64)
+    n = len(indptr) - 1
+    nnz = len(cols)
+    deg = np.diff(indptr)
+    rows = np.repeat(np.arange(n, dtype=np.int64), deg)
+    keys = rows * n + cols
+    if nnz and (np.any(np.diff(keys) <= 0) or not np.array_equal(np.sort(cols * n + rows), keys)):
+        raise ValueError("simmelian_host needs a canonical CSR with a symmetric pattern")
+    tpos = np.searchsorted(keys, cols * n + rows)
+    hasdiag = np.zeros(n, dtype=np.int64)
+    hasdiag[rows[rows == cols]] = 1
+    up = np.nonzero(rows < cols)[0]  # one unit of work per pair u < v
+    u, v = rows[up], cols[up]
+    ufirst = deg[u] <= deg[v]
+    a, b = np.where(ufirst, u, v), np.where(ufirst, v, u)  # a: the shorter list
+    mn = deg[a]
+    pid = np.repeat(np.arange(len(up), dtype=np.int64), mn)
+    ea = indptr[a][pid] + (np.arange(len(pid), dtype=np.int64) - np.repeat(np.cumsum(mn) - mn, mn))
+    w = cols[ea]
+    want = b[pid] * n + w
+    eb = np.minimum(np.searchsorted(keys, want), max(nnz - 1, 0))
+    hit = (keys[eb] == want) & (w != a[pid]) & (w != b[pid]) if nnz else np.zeros(0, dtype=bool)
+    pid, ea, eb = pid[hit], ea[hit], eb[hit]
+    c = np.bincount(pid, minlength=len(up)).astype(np.int64)  # common neighbours = triangles
+    t = np.full(nnz, -1, dtype=np.int64)  # the diagonal's sentinel ranks last
+    t[up] = c
+    t[tpos[up]] = c
+    order = np.lexsort((-t, rows))
+    st = t[order]  # every row's counts, descending
+    tmax = int(t.max()) if nnz else 0
+    K = tmax + 2
+    G = rows * K + (tmax - st)  # ascending: a row's position of a count by one search
+    rf = np.searchsorted(G, rows * K + (tmax - t), side="left") - indptr[rows]  # larger counts in the row
+    tp = c[pid]
+    m = np.maximum(rf[ea] - (tp > t[ea]), rf[eb] - (tp > t[eb]))
+    return dict(indptr=indptr, n=n, nnz=nnz, deg=deg, hasdiag=hasdiag, tpos=tpos, up=up, u=u, v=v,
+                c=c, t=t, st=st, tmax=tmax, K=K, G=G, rf=rf, pid=pid, m=m)
+
+
+def _simmelian_size(p, x, exy, k, txy):
+    """``|P_k(x|y)|`` for node ``x``, the entry ``exy`` of its alter ``y`` (count ``txy``)
+    and rank bound ``k`` (arrays): the row's sorted counts with one copy of ``txy`` taken
+    out at its first position; below the row's length the size is the end of the tie
+    group that holds position ``k - 1``."""
+    ip = p["indptr"]
+    L = p["deg"][x] - p["hasdiag"][x] - 1
+    full = k >= L
+    pos = p["rf"][exy]
+    j = np.minimum(k, np.maximum(L, 1)) - 1
+    jj = np.where(j < pos, j, j + 1)
+    val = p["st"][ip[x] + np.minimum(jj, p["deg"][x] - 1)]
+    ge = np.searchsorted(p["G"], x * p["K"] + (p["tmax"] - val), side="right") - ip[x]
+    return np.where(full, L, ge - (txy >= val))
+
+
+def simmelian_host(indptr, indices, max_rank: int = 0, prep=None):
+    """The Simmelian backbone score of every entry of a symmetric CSR pattern: the NumPy
+    specification of gs_simmelian, in the candidate form.  Returns ``(score, num, den)``:
+    float64 and two int64 arrays, one value per entry, ``score = num / den`` by one IEEE
+    division, equal on ``(u, v)`` and ``(v, u)``, 0 (``0 / 1``) on the diagonal.
+
+    On the simple undirected graph of the pattern: ``t(u, w)`` is the number of triangles
+    through {u, w}; for an edge {u, v} the ego ``u`` ranks ``N(u) \\ {v}`` by ``t``, ties
+    sharing the best rank (0-based), and ``P_k(u|v)`` holds the neighbours of rank below
+    ``k``.  ``max_rank = 0``: the largest Jaccard ratio of ``P_k(u|v)`` and ``P_k(v|u)``
+    over ``k >= 1``.  The intersection only grows at ``k = m_w + 1``, ``m_w`` the larger of
+    a common neighbour's two ranks, so with the ``m`` sorted candidate ``j`` (the last of
+    equal ``m``) is ``j / (|P_{m+1}(u|v)| + |P_{m+1}(v|u)| - j)``; the candidates are
+    compared exactly (cross-multiplied int64).  ``max_rank = k0 >= 1``: the overlap
+    ``|P_k0(u|v) ∩ P_k0(v|u)|`` itself, ``den = 1``."""
+    k0 = int(max_rank)
+    if k0 < 0:
+        raise ValueError(f"max_rank must be >= 0, got {max_rank}")
+    p = simmelian_prepare(indptr, indices) if prep is None else prep
+    up, tpos, pid, m = p["up"], p["tpos"], p["pid"], p["m"]
+    P = len(up)
+    num = np.zeros(P, dtype=np.int64)
+    den = np.ones(P, dtype=np.int64)
+    if k0 >= 1:
+        num = np.bincount(pid[m < k0], minlength=P).astype(np.int64)
+    elif len(pid):
+        o = np.lexsort((m, pid))
+        sp_, sm = pid[o], m[o]
+        start = np.concatenate([[0], np.cumsum(p["c"])])
+        j = np.arange(len(o), dtype=np.int64) - start[sp_] + 1
+        last = np.ones(len(o), dtype=bool)  # the last of equal m in its pair
+        last[:-1] = (sp_[1:] != sp_[:-1]) | (sm[1:] != sm[:-1])
+        cp, cj, ck = sp_[last], j[last], sm[last] + 1
+        txy = p["c"][cp]
+        cd = (_simmelian_size(p, p["u"][cp], up[cp], ck, txy)
+              + _simmelian_size(p, p["v"][cp], tpos[up[cp]], ck, txy) - cj)
+        # the best candidate of a pair: the largest quotient first (a correctly rounded
+        # division is monotone, so the exact maximum is among the largest quotients) ...
+        q = cj / cd
+        heads = np.nonzero(np.concatenate([[True], cp[1:] != cp[:-1]]))[0]
+        best = np.maximum.reduceat(q, heads)
+        pairs = cp[heads]
+        bq = np.zeros(P)
+        bq[pairs] = best
+        first = np.nonzero(q == bq[cp])[0]
+        first = first[np.concatenate([[True], cp[first][1:] != cp[first][:-1]])]
+        num[pairs], den[pairs] = cj[first], cd[first]
+        # ... then the exact check, and an exact scan of the pairs it fails on
+        for pr in np.unique(cp[cj * den[cp] > num[cp] * cd]):
+            for i in np.nonzero(cp == pr)[0]:
+                if int(cj[i]) * int(den[pr]) > int(num[pr]) * int(cd[i]):
+                    num[pr], den[pr] = cj[i], cd[i]
+    n_out = np.zeros(p["nnz"], dtype=np.int64)
+    d_out = np.ones(p["nnz"], dtype=np.int64)
+    n_out[up], d_out[up] = num, den
+    n_out[tpos[up]], d_out[tpos[up]] = num, den
+    return n_out / d_out, n_out, d_out
+
+
+def simmelian_bruteforce(indptr, indices, max_rank: int = 0):
+    """The literal definition of ``simmelian_host``: Python sets, every ``k`` at which a
+    ranked neighbourhood gains a member, ``fractions.Fraction``.  Slow and obviously right.  Returns one ``Fraction`` per entry (the overlap for ``max_rank >=
+    1``)."""
+    from fractions import Fraction
+
+    indptr = np.asarray(indptr, dtype=np.int64)
+    cols = np.asarray(indices, dtype=np.int64)
+    n = len(indptr) - 1
+    k0 = int(max_rank)
+    if k0 < 0:
+        raise ValueError(f"max_rank must be >= 0, got {max_rank}")
+    nb = [set(cols[indptr[x]:indptr[x + 1]].tolist()) - {x} for x in range(n)]
+    tri = {}
+
+    def t(x, y):
+        key = (x, y) if x < y else (y, x)
+        if key not in tri:
+            tri[key] = len(nb[x] & nb[y])
+        return tri[key]
+
+    by_t = {}
+
+    def ranked(x, y):
+        """(ranks, neighbours) of N(x) minus y by ascending rank: the rank of w is the
+        number of the others with strictly more triangles"""
+        if x not in by_t:
+            ws = np.array(sorted(nb[x]), dtype=np.int64)
+            ts = np.array([t(x, int(w)) for w in ws], dtype=np.int64)
+            o = np.argsort(-ts, kind="stable")
+            by_t[x] = (ws[o], ts[o])
+        ws, ts = by_t[x]
+        keep = ws != y
+        ws, ts = ws[keep], ts[keep]
+        rank = np.searchsorted(-ts, -ts, side="left")  # ts is descending
+        return rank, ws
+
+    def prefix(lst, cur, pos, k):
+        """the members of rank < k join ``cur``; ``pos`` of them were in already"""
+        new = int(np.searchsorted(lst[0], k, side="left"))
+        cur.update(lst[1][pos:new].tolist())
+        return new
+
+    res = [Fraction(0)] * len(cols)
+    pos_of = {}
+    for x in range(n):
+        for e in range(indptr[x], indptr[x + 1]):
+            pos_of[(x, int(cols[e]))] = e
+    for (x, y), e in pos_of.items():
+        if x >= y:
+            continue
+        lx, ly = ranked(x, y), ranked(y, x)
+        px, py, ix, iy = set(), set(), 0, 0
+        if k0 >= 1:
+            prefix(lx, px, 0, k0)
+            prefix(ly, py, 0, k0)
+            best = Fraction(len(px & py))
+        else:
+            best = Fraction(0)
+            # every k at which either set gains a member (k = a rank + 1): between two of
+            # them both sets, and so the ratio, stay what they were
+            for k in np.unique(np.concatenate([lx[0] + 1, ly[0] + 1, [1]])).tolist():
+                ix, iy = prefix(lx, px, ix, k), prefix(ly, py, iy, k)
+                inter = len(px & py)
+                if inter:
+                    best = max(best, Fraction(inter, len(px) + len(py) - inter))
+        res[e] = res[pos_of[(y, x)]] = best
+    return res
+
+
 def local_filter_scores(scores, edge_index, num_nodes: int, keep_lowest: bool = False):
     """The local-filter score of every ``edge_index`` column: the NumPy specification of
     gs_segment_rank and gs_local_scores (L-Spar, Satuluri et al.; Local Degree / Local

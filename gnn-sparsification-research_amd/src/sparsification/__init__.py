@@ -7,6 +7,7 @@ from gsparse import (  # noqa: F401
     calculate_effective_resistance_scores,
     calculate_feature_cosine_scores,
     calculate_jaccard_scores,
+    calculate_simmelian_scores,
     calculate_trussness_scores,
     compute_geodesic_preservation,
     compute_spectral_approximation,
@@ -25,6 +26,7 @@ __all__ = [
     "calculate_approx_effective_resistance_scores",
     "calculate_feature_cosine_scores",
     "calculate_trussness_scores",
+    "calculate_simmelian_scores",
     "compute_geodesic_preservation",
     "compute_topology_metrics",
     "compute_topology_preservation",

@@ -6,6 +6,7 @@ from gsparse.metrics import (  # noqa: F401
     calculate_effective_resistance_scores,
     calculate_feature_cosine_scores,
     calculate_jaccard_scores,
+    calculate_simmelian_scores,
     calculate_trussness_scores,
     compute_geodesic_preservation,
     compute_spectral_approximation,

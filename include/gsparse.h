@@ -686,6 +686,40 @@ int gs_local_scores(gs_ctx *ctx, const int32_t *rank, int r_loc, const int64_t *
                     int d_loc, const double *table, int t_loc, int64_t ntable, double *out,
                     int out_loc, int64_t *n_top);
 
+/* ---- the Simmelian backbone: ranked-neighbourhood overlap ---------------------
+ * (Nick, Lee, Cunningham, Brandes, ASONAM 2013; NetworKit's Simmelian
+ * sparsifiers.  Not in the reference; the NumPy specification is
+ * gsparse/selection.py: simmelian_host, the literal definition
+ * simmelian_bruteforce.)
+ * On the simple undirected graph of the resident CSR pattern (symmetric;
+ * diagonal entries take no part and score 0, the multiplicities are ignored):
+ * t(u, w) is the number of triangles through {u, w}.  For an edge {u, v} the ego
+ * u ranks N(u) \ {v} by t, ties sharing the best rank, 0-based:
+ * rho(w) = #{x in N(u) \ {v} : t(u, x) > t(u, w)}, and P_k(u|v) holds the
+ * neighbours of rank < k (a tie group enters whole), so the score is a property
+ * of the graph and not of the node numbering.
+ *   max_rank == 0   out = max over k >= 1 of |P_k(u|v) n P_k(v|u)| /
+ *                   |P_k(u|v) u P_k(v|u)|, 0 without a common neighbour.  The
+ *                   candidates -- one per distinct larger rank of a common
+ *                   neighbour -- are compared exactly in int64 and the result is
+ *                   one IEEE division: the specification's bits.
+ *   max_rank >= 1   out = |P_k(u|v) n P_k(v|u)| at k = max_rank, an exact integer
+ *                   (NetworKit's parametric form).
+ * out[e] (nnz float64 values, out_loc: GS_HOST / GS_DEVICE), out[e] ==
+ * out[tpos[e]].  *max_common = the most common neighbours of a pair,
+ * *nonzero_pairs = the pairs u < v with one; class_counts[0..ncounts): pairs per
+ * GS_SIM_* class, by the shorter of the two neighbour lists: WAVE (<= 64) one
+ * common neighbour per lane, MID (<= 512) a wave with an LDS slice, LDS (<= 8192)
+ * a workgroup ordering the ranks in LDS, STREAM a radix sort of the hubs' (pair,
+ * rank).  GSPARSE_SIM_WAVE_MAX / _MID_MAX / _LDS_MAX lower the bounds; they are
+ * read on every call and change class_counts only.  Integer atomics only: the
+ * same bytes on every run.  Each counter may be NULL.  GS_EINVAL for max_rank <
+ * 0; GS_EUNSUPPORTED for a directed adjacency or nnz >= 2^31 - 1; nnz == 0 gives
+ * an empty result and zeros. */
+enum { GS_SIM_WAVE = 0, GS_SIM_MID, GS_SIM_LDS, GS_SIM_STREAM, GS_SIM_CLASSES };
+int gs_simmelian(gs_ctx *ctx, double *out, int out_loc, int64_t max_rank, int64_t *max_common,
+                 int64_t *nonzero_pairs, int64_t *class_counts, int ncounts);
+
 #ifdef __cplusplus
 }
 #endif
