@@ -1,11 +1,10 @@
 // gs_core.hip -- context lifecycle, errors, profiling, copies, device-wide
-// primitives (rocPRIM radix sort / scan) for libgsparse.
+// primitives (rocPRIM scan; radix sort through gs_sort.hpp) for libgsparse.
 #include <cstdarg>
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "gs_internal.hpp"
+#include "gs_sort.hpp"
 
 namespace gs {
 
@@ -111,36 +110,20 @@ void exclusive_scan_i64(gs_ctx *c, const int64_t *in, int64_t *out, int64_t n) {
 }
 
 void sort_keys_u64(gs_ctx *c, uint64_t *keys, int64_t n, int end_bit) {
-    if (n <= 1) return;
-    DevBuf &alt = c->scratch[4];
-    uint64_t *k2 = (uint64_t *)alt.ensure(sizeof(uint64_t) * n);
-    rocprim::double_buffer<uint64_t> db(keys, k2);
-    size_t tmp = 0;
-    GS_HIP(rocprim::radix_sort_keys(nullptr, tmp, db, (size_t)n, 0, end_bit, c->stream));
-    void *t = c->scratch[5].ensure(tmp + 16);
-    GS_HIP(rocprim::radix_sort_keys(t, tmp, db, (size_t)n, 0, end_bit, c->stream));
-    if (db.current() != keys)
-        GS_HIP(hipMemcpyAsync(keys, db.current(), sizeof(uint64_t) * n, hipMemcpyDeviceToDevice,
-                              c->stream));
+    if (n <= 1) return;  // nothing to sort: no alternate either
+    uint64_t *k2 = (uint64_t *)c->scratch[4].ensure(sizeof(uint64_t) * n);
+    const uint64_t *r = radix_sort_keys(c, c->scratch[5], keys, k2, n, 0, end_bit, c->stream);
+    if (r != keys) GS_HIP(hipMemcpyAsync(keys, r, sizeof(uint64_t) * n, hipMemcpyDeviceToDevice, c->stream));
 }
 
 void sort_pairs_u64_i64(gs_ctx *c, uint64_t *keys, int64_t *vals, int64_t n, int end_bit) {
     if (n <= 1) return;
-    DevBuf &alt = c->scratch[4];
-    DevBuf &altv = c->scratch[3];
-    uint64_t *k2 = (uint64_t *)alt.ensure(sizeof(uint64_t) * n);
-    int64_t *v2 = (int64_t *)altv.ensure(sizeof(int64_t) * n);
-    rocprim::double_buffer<uint64_t> dk(keys, k2);
-    rocprim::double_buffer<int64_t> dv(vals, v2);
-    size_t tmp = 0;
-    GS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, dk, dv, (size_t)n, 0, end_bit, c->stream));
-    void *t = c->scratch[5].ensure(tmp + 16);
-    GS_HIP(rocprim::radix_sort_pairs(t, tmp, dk, dv, (size_t)n, 0, end_bit, c->stream));
-    if (dk.current() != keys) {
-        GS_HIP(hipMemcpyAsync(keys, dk.current(), sizeof(uint64_t) * n, hipMemcpyDeviceToDevice,
-                              c->stream));
-        GS_HIP(hipMemcpyAsync(vals, dv.current(), sizeof(int64_t) * n, hipMemcpyDeviceToDevice,
-                              c->stream));
+    uint64_t *k2 = (uint64_t *)c->scratch[4].ensure(sizeof(uint64_t) * n);
+    int64_t *v2 = (int64_t *)c->scratch[3].ensure(sizeof(int64_t) * n);
+    const auto r = radix_sort_pairs(c, c->scratch[5], keys, k2, vals, v2, n, 0, end_bit, c->stream);
+    if (r.keys != keys) {
+        GS_HIP(hipMemcpyAsync(keys, r.keys, sizeof(uint64_t) * n, hipMemcpyDeviceToDevice, c->stream));
+        GS_HIP(hipMemcpyAsync(vals, r.vals, sizeof(int64_t) * n, hipMemcpyDeviceToDevice, c->stream));
     }
 }
 

@@ -20,10 +20,9 @@
 // With expand, gs_undirected_ids names every column's unordered pair first, the rounds
 // mark pairs instead of columns, and one last pass writes mask[i] = marked[pair[i]].
 // The per-element rules are gs_forest.hpp's.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "gs_forest.hpp"
-#include "gs_internal.hpp"
+#include "gs_sort.hpp"
+#include "gs_wave.hpp"
 
 namespace gs {
 
@@ -111,7 +110,7 @@ k_forest_best(const P *__restrict__ win, int64_t W, const int32_t *__restrict__ 
             }
         }
         const unsigned long long m = __ballot(keep[k]);
-        before[k] = (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+        before[k] = lanes_below(m);
         if (lane == 0) cnt[k * 4 + wave] = (unsigned int)__popcll(m);
     }
     __syncthreads();
@@ -155,7 +154,7 @@ __global__ void k_forest_hook(int64_t n, const int32_t *__restrict__ lab, const 
         }
         hook[a] = to;
     }
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&st->hooked, mine);
 }
 
@@ -195,7 +194,7 @@ __global__ void k_forest_expand(const int64_t *__restrict__ pair, const uint8_t 
         mask[i] = m;
         mine += m;
     }
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&st->marked, mine);
 }
 
@@ -245,16 +244,7 @@ static ForestOut forest_run(gs_ctx *c, const double *ds, const int64_t *dsrc, co
     GS_HIP(hipGetLastError());
     const ForestState h0 = forest_read(c, st);
     GS_CHECK(!h0.bad, GS_EINVAL, "edge_index id out of range [0, %lld)", (long long)n);
-    const P *pos = pos0;
-    if (E > 1) {
-        rocprim::double_buffer<uint64_t> dk(key0, key1);
-        rocprim::double_buffer<P> dv(pos0, pos1);
-        size_t tmp = 0;
-        GS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, dk, dv, (size_t)E, 0, 64, s));
-        void *t = c->buf("forest_tmp").ensure(tmp + 16);
-        GS_HIP(rocprim::radix_sort_pairs(t, tmp, dk, dv, (size_t)E, 0, 64, s));
-        pos = dv.current();
-    }
+    const P *pos = radix_sort_pairs(c, c->buf("forest_tmp"), key0, key1, pos0, pos1, E, 0, 64, s).vals;
     k_forest_ends<P><<<gE, 256, 0, s>>>(dsrc, ddst, pos, E, keep_lowest, eu, ev);
     GS_HIP(hipGetLastError());
     // keys and ids read and written; eight 8-bit digit passes over the pairs and one

@@ -27,6 +27,7 @@
 // __host__ __device__ rules are also compiled for the host by tools/jac_host_check.cpp.
 #pragma once
 #include "gs_internal.hpp"
+#include "gs_util.hpp"
 
 namespace gs {
 
@@ -181,6 +182,10 @@ struct JacShares {
     int64_t E(int r) const { return cuts[P() + 1 + r]; }
     int64_t O(int r) const { return cuts[2 * (P() + 1) + r]; }
 };
+// the part that holds owner entry i: the last r < P of the ascending O with O[r] <= i
+__host__ __device__ __forceinline__ int jac_part_of(const int64_t *O, int P, int64_t i) {
+    return partition_point(P - 1, [=](int r) { return O[r + 1] <= i; });
+}
 
 // The GSPARSE_JAC* variables as they are now.  jac_knobs() (gs_jaccard.hip) is the only
 // reader of the environment in the Jaccard units; an entry point calls it once.
@@ -255,16 +260,6 @@ inline JacState &jac_state(gs_ctx *c) {
 // cc != nullptr: the part's raw counts into its compact owner-entry array
 void jaccard_symmetric(gs_ctx *c, const JacKnobs &k, double *out, int part, int nparts,
                        int counts = 0, uint32_t *cc = nullptr);
-// The triangle counts of the simple undirected graph of the pattern, as the trussness and
-// the Simmelian backbone start from them: the owner-side intersection kernels in count
-// mode (gs_common_neighbors) into device out[nnz] ...
-inline void support_pass(gs_ctx *c, double *out) { jaccard_symmetric(c, jac_knobs(), out, 0, 1, 1); }
-// ... less the stored diagonal entries of the two ends of an off-diagonal entry (r, c),
-// which that count includes: u (v) itself is a "common neighbour" of (u, v) when (u, u)
-// ((v, v)) is stored
-__host__ __device__ __forceinline__ int support_less_diag(double cnt, uint8_t diag_r, uint8_t diag_c) {
-    return (int)cnt - (int)diag_r - (int)diag_c;
-}
 // gs_jac_plan.hip: the kept plan of rows [r0, r1), or a new one; sum of squared degrees
 const JacPlan &jac_plan(gs_ctx *c, const JacKnobs &k, int64_t r0, int64_t r1);
 double jac_deg2(gs_ctx *c);

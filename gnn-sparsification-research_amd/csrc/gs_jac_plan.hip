@@ -3,6 +3,7 @@
 // bitmap rows cut into batches.  jac_plan() returns the kept plan when the graph and the
 // rows are the ones it was built for.
 #include "gs_jac.hpp"
+#include "gs_wave.hpp"
 
 namespace gs {
 
@@ -28,7 +29,7 @@ __global__ void __launch_bounds__(256) k_jac_plan(const int64_t *__restrict__ ip
                 const int64_t dv = ip[v + 1] - ip[v];
                 if (jac_owns(du, dv, (int32_t)u, v)) w += dv;
             }
-            for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o);
+            w = wave_sum(w);
         }
         if (lane == 0) {
             const int64_t nt = jac_row_tasks(k, du, w);
@@ -95,7 +96,7 @@ __global__ void k_jac_bytes(const int64_t *__restrict__ ip, int64_t n,
         const unsigned long long d = (unsigned long long)(ip[u + 1] - ip[u]);
         s += d * d;
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(acc, s);
 }
 

@@ -143,12 +143,7 @@ struct JacSortedProbe {
         return false;
     }
     __device__ __forceinline__ bool done(int32_t x, S) const {
-        int64_t lo = 0, hi = du;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (row[mid] < x) lo = mid + 1;
-            else hi = mid;
-        }
+        const int64_t lo = lower_bound(row, du, x);
         return lo < du && row[lo] == x;
     }
 };

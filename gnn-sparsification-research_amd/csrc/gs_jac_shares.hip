@@ -4,6 +4,7 @@
 // into the score of every entry.  gs_jaccard_shares, gs_jaccard_part_counts,
 // gs_jaccard_from_counts.
 #include "gs_jac.hpp"
+#include "gs_wave.hpp"
 
 namespace gs {
 
@@ -25,7 +26,7 @@ __global__ void __launch_bounds__(256) k_jac_rowwork(const int64_t *__restrict__
             const int64_t dv = ip[v + 1] - ip[v];
             if (jac_owns(du, dv, (int32_t)u, v)) w += k < 0 ? du + dv : dv;
         }
-        for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o);
+        w = wave_sum(w);
         if (lane == 0) work[u] = w + jac_row_tasks(k, du, w) * du;
     }
 }
@@ -70,19 +71,8 @@ __global__ void k_jac_cuts(const int64_t *__restrict__ S, const int64_t *__restr
     const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (r > P) return;
     const int64_t total = S[n];
-    int64_t R;
-    if (r == 0) R = 0;
-    else if (r == P) R = n;
-    else {
-        const int64_t t = total * r / P;
-        int64_t lo = 0, hi = n;  // first u in [0, n] with S[u] >= t
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (S[mid] >= t) hi = mid;
-            else lo = mid + 1;
-        }
-        R = lo;
-    }
+    // first u in [0, n] with S[u] >= total * r / P
+    const int64_t R = r == 0 ? 0 : r == P ? n : lower_bound(S, n, total * r / P);
     out[r] = R;
     out[P + 1 + r] = ip[R];
     out[2 * (P + 1) + r] = opre[ip[R]];
@@ -98,12 +88,7 @@ __global__ void k_jac_scatter_owners(const int32_t *__restrict__ opos, const int
     const int64_t *O = cuts + 2 * (P + 1);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nown;
          i += (int64_t)gridDim.x * blockDim.x) {
-        int lo = 0, hi = P - 1;  // last part r with O[r] <= i
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (O[mid] <= i) lo = mid;
-            else hi = mid - 1;
-        }
+        const int lo = jac_part_of(O, P, i);
         const int64_t cnt = cc[lo * stride + (i - O[lo])];
         const double uni = (double)osum[i] - (double)cnt;
         const double val = uni > 0.0 ? (double)cnt / uni : 0.0;

@@ -22,6 +22,7 @@
 //           code index cached per graph and part count)
 // The mask is bit-identical to gs_topk_mask on the gathered scores (the device tie rule).
 #include "gs_jac.hpp"
+#include "gs_wave.hpp"
 
 #include <map>
 #include <mutex>
@@ -132,34 +133,18 @@ __global__ void k_jsel_ties(const uint64_t *__restrict__ keys, const int32_t *__
     const uint64_t cut = st->prefix;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t trips = (np + stride - 1) / stride;
-    const int lane = threadIdx.x & 63;
     for (int64_t tr = 0, i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; tr < trips; ++tr, i += stride) {
         const bool tie = i < np && keys[i] == cut;
         const int two = tie && opos[obase + i] != orev[obase + i] ? 1 : 0;
         const unsigned long long m = __ballot(tie), m2 = __ballot(two != 0);
         if (!m) continue;
-        const int leader = __builtin_ctzll(m);
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(&st->ntie, (unsigned long long)(__popcll(m) + __popcll(m2)));
-        base = __shfl(base, leader, 64);
-        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long base = wave_reserve((unsigned long long)(__popcll(m) + __popcll(m2)), &st->ntie);
         if (tie) {
-            const unsigned long long p = base + __popcll(m & below) + __popcll(m2 & below);
+            const unsigned long long p = base + lanes_below(m) + lanes_below(m2);
             pos[p] = opos[obase + i];
             if (two) pos[p + 1] = orev[obase + i];
         }
     }
-}
-
-// rank of position x in the sorted tie block (every tied position is in it)
-__device__ __forceinline__ int64_t jsel_tie_rank(const uint64_t *__restrict__ tall, int64_t ntie, uint64_t x) {
-    int64_t lo = 0, hi = ntie;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (tall[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // mode 0: ties none kept, 1: all kept, 2: by rank in the sorted block.  Keep codes are
@@ -170,8 +155,9 @@ __device__ __forceinline__ uint32_t jsel_code(uint64_t k, uint64_t cut, int keep
                                               int32_t pa, int32_t pb) {
     if (k != cut) return (keep_lowest ? k < cut : k > cut) ? 3u : 0u;
     if (mode != 2) return mode ? 3u : 0u;
-    const int64_t ra = jsel_tie_rank(tall, ntie, (uint64_t)pa);
-    const int64_t rb = jsel_tie_rank(tall, ntie, (uint64_t)pb);
+    // the ranks of the two positions in the sorted tie block (every tied position is in it)
+    const int64_t ra = lower_bound(tall, ntie, (uint64_t)pa);
+    const int64_t rb = lower_bound(tall, ntie, (uint64_t)pb);
     const bool ka = keep_lowest ? ra < need : ra >= ntie - need;
     const bool kb = keep_lowest ? rb < need : rb >= ntie - need;
     return (ka ? 1u : 0u) | (kb ? 2u : 0u);
@@ -205,12 +191,7 @@ __global__ void k_jsel_slots(const int32_t *__restrict__ opos, const int32_t *__
                              uint32_t *__restrict__ slot) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nown;
          i += (int64_t)gridDim.x * blockDim.x) {
-        int lo = 0, hi = P - 1;  // last part r with O[r] <= i
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (O[mid] <= i) lo = mid;
-            else hi = mid - 1;
-        }
+        const int lo = jac_part_of(O, P, i);
         const uint32_t s = (uint32_t)(4 * lo * stride + (i - O[lo]));
         slot[opos[i]] = s;
         if (orev[i] != opos[i]) slot[orev[i]] = s | 0x80000000u;

@@ -8,10 +8,9 @@
 // gs_random_mask is random.py:45-49: gs_topk_mask's select of the n_keep highest
 // undirected scores into context scratch, then mask[i] = keep_undir[inverse[i]].
 // The per-element logic is gs_random.hpp's.
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "gs_internal.hpp"
 #include "gs_random.hpp"
+#include "gs_sort.hpp"
+#include "gs_wave.hpp"
 
 namespace gs {
 
@@ -74,7 +73,7 @@ __global__ void k_rand_gather(const uint8_t *__restrict__ keep, int64_t m, const
         mask[i] = w < 0 ? (uint8_t)0 : keep[w];
         bad += w < 0;
     }
-    for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off, 64);
+    bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&st->n_bad, bad);
 }
 
@@ -82,17 +81,12 @@ __global__ void k_rand_gather(const uint8_t *__restrict__ keep, int64_t m, const
 // (the caller's buffers or scratch[4] / scratch[3]: no copy back)
 template <class P>
 static void sort_pairs(gs_ctx *c, uint64_t *&keys, P *&vals, int64_t n, int end_bit) {
-    if (n <= 1) return;
+    if (n <= 1) return;  // nothing to sort: no alternates either
     uint64_t *k2 = (uint64_t *)c->scratch[4].ensure(sizeof(uint64_t) * n);
     P *v2 = (P *)c->scratch[3].ensure(sizeof(P) * n);
-    rocprim::double_buffer<uint64_t> dk(keys, k2);
-    rocprim::double_buffer<P> dv(vals, v2);
-    size_t tmp = 0;
-    GS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, dk, dv, (size_t)n, 0, end_bit, c->stream));
-    void *t = c->scratch[5].ensure(tmp + 16);
-    GS_HIP(rocprim::radix_sort_pairs(t, tmp, dk, dv, (size_t)n, 0, end_bit, c->stream));
-    keys = dk.current();
-    vals = dv.current();
+    const auto r = radix_sort_pairs(c, c->scratch[5], keys, k2, vals, v2, n, 0, end_bit, c->stream);
+    keys = r.keys;
+    vals = r.vals;
 }
 
 template <class P>

@@ -10,7 +10,7 @@
 // position in the grouped list: the scatter of an unsorted src places columns in atomic
 // order, the ranks are the same bytes on every run all the same.
 //
-// Segments and node lists: gs_seg.hpp (shared with gs_segment_topk).  Ranks by length:
+// Segments and node lists: seg_build (gs_seg.hpp, shared with gs_segment_topk).  Ranks by length:
 //   d <= 64      SHORT     sub-wave groups of 8 / 16 / 64 lanes, one (k, c) per lane; the
 //                          rank is a count over the group of the pairs that are larger:
 //                          each key is read once, each rank written once.  The count is
@@ -43,10 +43,10 @@
 // -- order-preserving, exact, independent of the arrival order; out = 1 - y.
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "gs_keys.hpp"
 #include "gs_seg.hpp"
+#include "gs_sort.hpp"
+#include "gs_wave.hpp"
 
 namespace gs {
 
@@ -337,17 +337,9 @@ static int segr_bits(uint64_t v) {
 // sorted copies afterwards
 static void segr_sort_pairs(gs_ctx *c, uint64_t *&key, uint64_t *&key2, uint32_t *&val, uint32_t *&val2,
                             int64_t S, int bits) {
-    if (S <= 1) return;
-    rocprim::double_buffer<uint64_t> dk(key, key2);
-    rocprim::double_buffer<uint32_t> dv(val, val2);
-    size_t tmp = 0;
-    GS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, dk, dv, (size_t)S, 0, bits, c->stream));
-    void *t = c->buf("segr_tmp").ensure(tmp + 16);
-    GS_HIP(rocprim::radix_sort_pairs(t, tmp, dk, dv, (size_t)S, 0, bits, c->stream));
-    key = dk.current();
-    key2 = dk.alternate();
-    val = dv.current();
-    val2 = dv.alternate();
+    const auto r = radix_sort_pairs(c, c->buf("segr_tmp"), key, key2, val, val2, S, 0, bits, c->stream);
+    if (r.keys != key) std::swap(key, key2);
+    if (r.vals != val) std::swap(val, val2);
 }
 
 // The ranks of the S columns of the STREAM list's segments; all: these are all E columns.
@@ -368,16 +360,9 @@ static void segr_stream(gs_ctx *c, const double *ds, const int64_t *dsrc, const 
         GS_HIP(hipMemsetAsync(cursor, 0, sizeof(unsigned long long), st));
         k_segr_gather<<<grid_for(n, 1, 1024), 256, 0, st>>>(sb.off, sb.cols, sb.hdr, sb.list, SL_STREAM, S,
                                                             cursor, val);
-        if (S > 1) {  // into column order
-            const int bits = segr_bits((uint64_t)(E - 1));
-            rocprim::double_buffer<uint32_t> dv(val, val2);
-            size_t tmp = 0;
-            GS_HIP(rocprim::radix_sort_keys(nullptr, tmp, dv, (size_t)S, 0, bits, st));
-            void *t = c->buf("segr_tmp").ensure(tmp + 16);
-            GS_HIP(rocprim::radix_sort_keys(t, tmp, dv, (size_t)S, 0, bits, st));
-            val = dv.current();
-            val2 = dv.alternate();
-        }
+        // into column order
+        if (radix_sort_keys(c, c->buf("segr_tmp"), val, val2, S, 0, segr_bits((uint64_t)(E - 1)), st) != val)
+            std::swap(val, val2);
     }
     k_segr_sortkey<false><<<g, 256, 0, st>>>(ds, dsrc, val, S, key);
     segr_sort_pairs(c, key, key2, val, val2, S, 64);
@@ -438,7 +423,7 @@ __global__ void __launch_bounds__(256) k_local_out(const int64_t *__restrict__ p
         out[i] = v;
         top += v == 1.0;
     }
-    for (int o = 32; o > 0; o >>= 1) top += __shfl_down(top, o, 64);
+    top = wave_sum(top);
     if ((threadIdx.x & 63) == 0 && top) atomicAdd(&hdr->n_top, top);
 }
 
@@ -468,8 +453,8 @@ extern "C" int gs_segment_rank(gs_ctx *c, const double *scores, int s_loc, int64
         const bool sort_all = mode && !strcmp(mode, "sort");
         const int lowest = keep_lowest ? 1 : 0;
         // sort mode: no segment is SHORT or LDS
-        const int smax = sort_all ? 0 : segk_limit("GSPARSE_SEGR_SHORT_MAX", kSegkShortMax);
-        const int lmax = sort_all ? 0 : segk_limit("GSPARSE_SEGR_LDS_MAX", kSegrLdsMax);
+        const int smax = sort_all ? 0 : knob_limit(getenv("GSPARSE_SEGR_SHORT_MAX"), kSegkShortMax);
+        const int lmax = sort_all ? 0 : knob_limit(getenv("GSPARSE_SEGR_LDS_MAX"), kSegrLdsMax);
         const int64_t E1 = E ? E : 1;
         const double *ds = (const double *)to_device(c, c->buf("segr_s"), scores, sizeof(double) * E, s_loc);
         const int64_t *dsrc = (const int64_t *)to_device(c, c->buf("segr_src"), src, sizeof(int64_t) * E,

@@ -7,7 +7,7 @@
 // Otherwise (or with a NaN in the segment) np.argsort's order decides inside the tie
 // block: status 2, no byte set, the caller makes the reference's own call.
 //
-// Segments and node lists: gs_seg.hpp.  Selection by length:
+// Segments and node lists: seg_build (gs_seg.hpp).  Selection by length:
 //   d <= k                 every column (handled by the kernel of its length)
 //   d <= 64      SHORT     sub-wave groups of 8 / 16 / 64 lanes, one key per lane; the
 //                          rank is a count of greater / equal keys over the group
@@ -17,6 +17,7 @@
 // Nothing waits for the host before the one copy that returns the counts.
 #include "gs_keys.hpp"
 #include "gs_seg.hpp"
+#include "gs_wave.hpp"
 
 namespace gs {
 
@@ -188,10 +189,8 @@ __global__ void __launch_bounds__(256) k_segk_tally(int64_t n, int64_t k, const 
         if (st == 1) g += (unsigned long long)(d < k ? d : k);
         a += st == 2;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        g += __shfl_down(g, o, 64);
-        a += __shfl_down(a, o, 64);
-    }
+    g = wave_sum(g);
+    a = wave_sum(a);
     if ((threadIdx.x & 63) == 0) {
         if (g) atomicAdd(&hdr->nguar, g);
         if (a) atomicAdd(&hdr->namb, a);
@@ -217,8 +216,8 @@ extern "C" int gs_segment_topk(gs_ctx *c, const double *scores, int s_loc, int64
         GS_CHECK(ncounts >= 0 && (ncounts == 0 || class_counts), GS_EINVAL, "class_counts is null");
         GS_HIP(hipSetDevice(c->device));
         hipStream_t st = c->stream;
-        const int smax = segk_limit("GSPARSE_SEGK_SHORT_MAX", kSegkShortMax);
-        const int lmax = segk_limit("GSPARSE_SEGK_LDS_MAX", kSegkLdsMax);
+        const int smax = knob_limit(getenv("GSPARSE_SEGK_SHORT_MAX"), kSegkShortMax);
+        const int lmax = knob_limit(getenv("GSPARSE_SEGK_LDS_MAX"), kSegkLdsMax);
         const int64_t E1 = E ? E : 1, n1 = n ? n : 1;
         const double *ds = (const double *)to_device(c, c->buf("segk_s"), scores, sizeof(double) * E, s_loc);
         const int64_t *dsrc = (const int64_t *)to_device(c, c->buf("segk_src"), src, sizeof(int64_t) * E,

@@ -1,15 +1,12 @@
 // gs_sim.hpp -- the Simmelian backbone's host-side rules (gs_simmelian.hip): the pair
-// classes, their bounds and the knobs that lower them.  Host and device code; also
-// compiled for the host alone by tools/sim_host_check.cpp.
+// classes, their bounds and the knobs that lower them (gs_util.hpp's knob_limit).  Host and
+// device code; also compiled for the host alone by tools/sim_host_check.cpp.
 #pragma once
 
 #include <cstdint>
 #include <cstdlib>
 
-#ifndef __host__
-#define __host__
-#define __device__
-#endif
+#include "gs_util.hpp"
 
 namespace gs {
 
@@ -24,18 +21,11 @@ struct SimBounds {
     int wave, mid, lds;
 };
 
-// a knob's text -> a bound in [0, dflt]: it can only lower the class limit
-inline int sim_limit_text(const char *e, int dflt) {
-    if (!e || !*e) return dflt;
-    const long v = atol(e);
-    return v < 0 ? 0 : v > dflt ? dflt : (int)v;
-}
-
-// GSPARSE_SIM_WAVE_MAX / _MID_MAX / _LDS_MAX as they are now
+// GSPARSE_SIM_WAVE_MAX / _MID_MAX / _LDS_MAX as they are now (knob_limit: they only lower)
 inline SimBounds sim_bounds() {
-    return SimBounds{sim_limit_text(getenv("GSPARSE_SIM_WAVE_MAX"), kSimWaveMax),
-                     sim_limit_text(getenv("GSPARSE_SIM_MID_MAX"), kSimMidMax),
-                     sim_limit_text(getenv("GSPARSE_SIM_LDS_MAX"), kSimLdsMax)};
+    return SimBounds{knob_limit(getenv("GSPARSE_SIM_WAVE_MAX"), kSimWaveMax),
+                     knob_limit(getenv("GSPARSE_SIM_MID_MAX"), kSimMidMax),
+                     knob_limit(getenv("GSPARSE_SIM_LDS_MAX"), kSimLdsMax)};
 }
 
 __host__ __device__ inline int sim_class(int64_t shorter, const SimBounds &b) {

@@ -25,7 +25,8 @@
 //            the sorted row with one copy of t(u, v) skipped (sim_size)
 //   pairs    one unit of work per upper entry u < v, both directions written through
 //            tpos: the lanes stride the shorter sorted neighbour list and binary-search the
-//            longer (k_truss_peel's scheme); a hit's two entry positions give m_w.  By the
+//            longer (gs_tri.hpp's common_pos, as k_truss_peel); a hit's two entry positions
+//            give m_w; lists and keys are appended with gs_wave.hpp's wave_append.  By the
 //            shorter list's length, an upper bound on the common neighbours:
 //              WAVE   <= 64    one m per lane; j and "the last of equal m" by cross-lane
 //                              counts; no LDS
@@ -39,10 +40,10 @@
 // GSPARSE_SIM_WAVE_MAX / _MID_MAX / _LDS_MAX lower the class bounds (gs_sim.hpp); the
 // scores do not depend on them.  No kernel reads plain memory that another workgroup
 // writes in the same launch: every stage is its own launch.
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "gs_jac.hpp"
 #include "gs_sim.hpp"
+#include "gs_sort.hpp"
+#include "gs_tri.hpp"
+#include "gs_wave.hpp"
 
 namespace gs {
 
@@ -67,42 +68,21 @@ struct SimG {
 };
 
 struct SimPair {
-    int64_t e, er, pa, pb;  // the entry (u, v), its reverse, the starts of the shorter / longer list
-    int32_t u, v, da, db, tuv;
+    int64_t e, er;  // the entry (u, v) and its reverse
+    int32_t u, v, tuv;
+    TriRows l;      // the shorter and the longer of the two rows
 };
 
 __device__ __forceinline__ SimPair sim_pair(const SimG &g, int64_t e) {
-    SimPair p;
-    p.e = e;
-    p.er = g.tpos[e];
-    p.u = g.rows[e];
-    p.v = g.ix[e];
-    p.tuv = g.tt[e];
-    const int64_t pu = g.ip[p.u], pv = g.ip[p.v];
-    const int32_t du = (int32_t)(g.ip[p.u + 1] - pu), dv = (int32_t)(g.ip[p.v + 1] - pv);
-    const bool ufirst = du <= dv;
-    p.pa = ufirst ? pu : pv;
-    p.pb = ufirst ? pv : pu;
-    p.da = ufirst ? du : dv;
-    p.db = ufirst ? dv : du;
-    return p;
+    const int32_t u = g.rows[e], v = g.ix[e];
+    return SimPair{e, g.tpos[e], u, v, g.tt[e], TriRows(g.ip, u, v)};
 }
 
-// entry i < da of the shorter list: m_w when it is a common neighbour w, else -1
+// entry i < l.da of the shorter row: m_w when it is a common neighbour w, else -1
 __device__ __forceinline__ int32_t sim_probe(const SimG &g, const SimPair &p, int32_t i) {
-    const int32_t w = g.ix[p.pa + i];
-    if (w == p.u || w == p.v) return -1;
-    const int32_t *__restrict__ lb = g.ix + p.pb;
-    int32_t lo = 0, hi = p.db;
-    while (lo < hi) {
-        const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
-        if (lb[mid] < w)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    if (lo >= p.db || lb[lo] != w) return -1;
-    const int64_t ea = p.pa + i, eb = p.pb + lo;
+    const int32_t at = common_pos(g.ix, p.l, p.u, p.v, i);
+    if (at < 0) return -1;
+    const int64_t ea = p.l.pa + i, eb = p.l.pb + at;
     const int32_t ma = g.rf[ea] - (p.tuv > g.tt[ea]), mb = g.rf[eb] - (p.tuv > g.tt[eb]);
     return ma > mb ? ma : mb;
 }
@@ -117,14 +97,9 @@ __device__ __forceinline__ int64_t sim_size(const SimG &g, int32_t x, int64_t ex
     if (k >= L) return L;
     const int32_t pos = g.rf[exy], j = k - 1;
     const int32_t val = g.st[base + (j < pos ? j : j + 1)];  // j + 1 <= L - 1 < d
-    int32_t lo = 0, hi = d;  // the first position with a count < val (the diagonal's -1 included)
-    while (lo < hi) {
-        const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
-        if (g.st[base + mid] >= val)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
+    // the first position with a count < val (the diagonal's -1 included)
+    const int32_t *__restrict__ row = g.st + base;
+    const int32_t lo = partition_point(d, [=](int32_t q) { return row[q] >= val; });
     return (int64_t)lo - (txy >= val);
 }
 
@@ -200,15 +175,8 @@ __global__ void __launch_bounds__(256) k_sim_rf(const int32_t *__restrict__ rows
          e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t base = ip[rows[e]];
         const int32_t t = tt[e];
-        int32_t lo = 0, hi = (int32_t)(ip[rows[e] + 1] - base);  // the first position with a count <= t
-        while (lo < hi) {
-            const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
-            if (st[base + mid] > t)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        rf[e] = lo;
+        // the first position with a count <= t
+        rf[e] = partition_point((int32_t)(ip[rows[e] + 1] - base), [=](int32_t q) { return st[base + q] > t; });
     }
 }
 
@@ -261,15 +229,8 @@ __global__ void __launch_bounds__(256) k_sim_lists(const int32_t *__restrict__ r
         int64_t shorter = 0;
         const int k = e < nnz ? sim_entry_class(rows, idx, ip, e, b, shorter) : -1;
         for (int q = 0; q < SIM_CLASSES; ++q) {
-            const unsigned long long mk = __ballot(k == q);
-            if (!mk) continue;
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(&hdr->fill[q], (unsigned long long)__popcll(mk));
-            at = __shfl((long long)at, 0, 64);
-            if (k == q) {
-                const int64_t p = bs.at[q] + (int64_t)at + __popcll(mk & ((1ull << lane) - 1ull));
-                if (p < bs.at[q + 1]) list[p] = (int32_t)e;  // always: the counts are the classify pass's
-            }
+            const int64_t p = bs.at[q] + (int64_t)wave_append(k == q, &hdr->fill[q]);
+            if (k == q && p < bs.at[q + 1]) list[p] = (int32_t)e;  // always: the counts are the classify pass's
         }
     }
 }
@@ -284,7 +245,7 @@ __global__ void __launch_bounds__(256) k_sim_wave(SimG g, const int32_t *__restr
     unsigned long long nz = 0;
     for (int64_t it = gw; it < total; it += nw) {  // wave-uniform trips
         const SimPair p = sim_pair(g, list[it]);
-        const int32_t m = lane < p.da ? sim_probe(g, p, lane) : -1;
+        const int32_t m = lane < p.l.da ? sim_probe(g, p, lane) : -1;
         const unsigned int c = (unsigned int)__popcll(__ballot(m >= 0));
         if (!c) continue;  // out is zeroed
         maxc = c > maxc ? c : maxc;
@@ -295,7 +256,7 @@ __global__ void __launch_bounds__(256) k_sim_wave(SimG g, const int32_t *__restr
             continue;
         }
         int32_t j = 0, later = 0;  // hits of rank <= m; hits of the same rank in a higher lane
-        for (int r = 0; r < p.da && r < 64; ++r) {
+        for (int r = 0; r < p.l.da && r < 64; ++r) {
             const int32_t om = __shfl(m, r, 64);
             j += om >= 0 && om <= m;
             later += om == m && r > lane;
@@ -324,13 +285,13 @@ __global__ void __launch_bounds__(256) k_sim_mid(SimG g, const int32_t *__restri
         const int64_t it = g0 + w;
         const bool have = it < total;
         SimPair p = sim_pair(g, list[have ? it : total - 1]);
-        if (!have || p.da > kSimMidMax) p.da = 0;
+        if (!have || p.l.da > kSimMidMax) p.l.da = 0;
         int32_t c = 0, o = 0;
-        for (int32_t i0 = 0; i0 < p.da; i0 += 64) {  // wave-uniform trips
+        for (int32_t i0 = 0; i0 < p.l.da; i0 += 64) {  // wave-uniform trips
             const int32_t i = i0 + lane;
-            const int32_t m = i < p.da ? sim_probe(g, p, i) : -1;
+            const int32_t m = i < p.l.da ? sim_probe(g, p, i) : -1;
             const unsigned long long mk = __ballot(m >= 0);
-            if (m >= 0 && k0 == 0) ms[w][c + __popcll(mk & ((1ull << lane) - 1ull))] = m;  // c + 63 < da
+            if (m >= 0 && k0 == 0) ms[w][c + lanes_below(mk)] = m;  // c + 63 < da
             c += __popcll(mk);
             o += __popcll(__ballot(m >= 0 && m < k0));
         }
@@ -379,21 +340,17 @@ __global__ void __launch_bounds__(kSimLdsThreads) k_sim_lds(SimG g, const int32_
     unsigned long long nz = 0;
     for (int64_t it = blockIdx.x; it < total; it += gridDim.x) {  // the same in every thread
         const SimPair p = sim_pair(g, list[it]);
-        if (k0 == 0 && p.da > kSimLdsMax) continue;  // never: the class bound
+        if (k0 == 0 && p.l.da > kSimLdsMax) continue;  // never: the class bound
         if (tid == 0) n_hit = n_low = 0;
         __syncthreads();
-        for (int32_t i0 = 0; i0 < p.da; i0 += kSimLdsThreads) {  // workgroup-uniform trips
+        for (int32_t i0 = 0; i0 < p.l.da; i0 += kSimLdsThreads) {  // workgroup-uniform trips
             const int32_t i = i0 + tid;
-            const int32_t m = i < p.da ? sim_probe(g, p, i) : -1;
+            const int32_t m = i < p.l.da ? sim_probe(g, p, i) : -1;
             const unsigned long long mk = __ballot(m >= 0), lk = __ballot(m >= 0 && m < k0);
             if (!mk) continue;
-            unsigned int at = 0;
-            if (lane == 0) {
-                at = atomicAdd(&n_hit, (unsigned int)__popcll(mk));
-                if (lk) atomicAdd(&n_low, (unsigned int)__popcll(lk));
-            }
-            at = __shfl(at, 0, 64);
-            if (m >= 0 && k0 == 0) ms[at + __popcll(mk & ((1ull << lane) - 1ull))] = (uint32_t)m;  // < da
+            const unsigned int at = wave_reserve((unsigned int)__popcll(mk), &n_hit);
+            if (lk) wave_reserve((unsigned int)__popcll(lk), &n_low);
+            if (m >= 0 && k0 == 0) ms[at + lanes_below(mk)] = (uint32_t)m;  // < da
         }
         __syncthreads();
         const int32_t c = (int32_t)n_hit;
@@ -453,18 +410,12 @@ __global__ void __launch_bounds__(kSimLdsThreads) k_sim_lds(SimG g, const int32_
 // a cursor: one atomic per wave and step.  The unused keys stay all ones and sort last.
 __global__ void __launch_bounds__(256) k_sim_gather(SimG g, const int32_t *__restrict__ list, int64_t total, int64_t S,
                                                     SimHdr *__restrict__ hdr, uint64_t *__restrict__ keys) {
-    const int lane = threadIdx.x & 63;
     for (int64_t s = blockIdx.x; s < total; s += gridDim.x) {
         const SimPair p = sim_pair(g, list[s]);
-        for (int32_t i0 = 0; i0 < p.da; i0 += 256) {  // workgroup-uniform trips
+        for (int32_t i0 = 0; i0 < p.l.da; i0 += 256) {  // workgroup-uniform trips
             const int32_t i = i0 + (int32_t)threadIdx.x;
-            const int32_t m = i < p.da ? sim_probe(g, p, i) : -1;
-            const unsigned long long mk = __ballot(m >= 0);
-            if (!mk) continue;
-            unsigned long long at = 0;
-            if (lane == 0) at = atomicAdd(&hdr->scur, (unsigned long long)__popcll(mk));
-            at = __shfl((long long)at, 0, 64);
-            const int64_t q = (int64_t)at + __popcll(mk & ((1ull << lane) - 1ull));
+            const int32_t m = i < p.l.da ? sim_probe(g, p, i) : -1;
+            const int64_t q = (int64_t)wave_append(m >= 0, &hdr->scur);
             if (m >= 0 && q < S) keys[q] = ((uint64_t)s << 32) | (uint32_t)m;  // always: S sums the lists
         }
     }
@@ -481,18 +432,7 @@ __global__ void __launch_bounds__(256) k_sim_stream(SimG g, const int32_t *__res
     for (int64_t s = blockIdx.x; s < total; s += gridDim.x) {  // the same in every thread
         const SimPair p = sim_pair(g, list[s]);
         int64_t b[2];
-        for (int h = 0; h < 2; ++h) {  // the first key >= (s + h) << 32
-            const uint64_t want = (uint64_t)(s + h) << 32;
-            int64_t lo = 0, hi = S;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (keys[mid] < want)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            b[h] = lo;
-        }
+        for (int h = 0; h < 2; ++h) b[h] = lower_bound(keys, S, (uint64_t)(s + h) << 32);  // the first key >= (s + h) << 32
         const int64_t c = b[1] - b[0];
         if (c == 0) continue;
         if (tid == 0) {
@@ -619,14 +559,7 @@ static SimOut sim_run(gs_ctx *c, double *dout, int32_t k0) {
         GS_HIP(hipMemsetAsync(key, 0xFF, sizeof(uint64_t) * S, st));
         k_sim_gather<<<grid_for(nstr, 1, 4096), 256, 0, st>>>(sg, list + bs.at[SIM_STREAM], nstr, S, hdr, key);
         GS_HIP(hipGetLastError());
-        if (S > 1) {
-            rocprim::double_buffer<uint64_t> dk(key, key2);
-            size_t tmp = 0;
-            GS_HIP(rocprim::radix_sort_keys(nullptr, tmp, dk, (size_t)S, 0, 64, st));
-            void *t = c->buf("sim_tmp").ensure(tmp + 16);
-            GS_HIP(rocprim::radix_sort_keys(t, tmp, dk, (size_t)S, 0, 64, st));
-            key = dk.current();
-        }
+        key = radix_sort_keys(c, c->buf("sim_tmp"), key, key2, S, 0, 64, st);
         k_sim_stream<<<grid_for(nstr, 1, 4096), 256, 0, st>>>(sg, list + bs.at[SIM_STREAM], nstr, S, key, dout, hdr);
         GS_HIP(hipGetLastError());
         // the keys filled, written, sorted in eight digit passes and read; per hit two ranks and two counts

@@ -7,6 +7,7 @@
 // tie flags.  NaN orders last (np.sort), -0.0 == +0.0.
 #include "gs_internal.hpp"
 #include "gs_keys.hpp"
+#include "gs_wave.hpp"
 
 namespace gs {
 
@@ -67,10 +68,8 @@ __global__ void k_cut_counts(const double *__restrict__ s, int64_t nnz, const Se
         tie[i] = (k == t) ? 1 : 0;
     }
     // wave reduce then one atomic per wave
-    for (int off = 32; off > 0; off >>= 1) {
-        beyond += __shfl_down(beyond, off, 64);
-        eq += __shfl_down(eq, off, 64);
-    }
+    beyond = wave_sum(beyond);
+    eq = wave_sum(eq);
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&cnts[0], beyond);
         atomicAdd(&cnts[1], eq);
@@ -155,20 +154,8 @@ __global__ void __launch_bounds__(256) k_pick12(Sel12 *st, int keep_lowest) {
     }
 }
 
-// one global atomic per wave and trip (the cut's bucket may hold millions of scores)
-__device__ __forceinline__ unsigned long long wave_slot(bool take, unsigned long long *cnt) {
-    const unsigned long long m = __ballot(take);
-    if (!m) return 0;
-    const int lane = threadIdx.x & 63;
-    const int leader = __builtin_ctzll(m);
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(cnt, (unsigned long long)__popcll(m));
-    base = __shfl(base, leader, 64);
-    return base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 // block b compacts its range [b chunk, (b + 1) chunk) into the same range of ckey
-// (slots from an LDS counter, one LDS atomic per wave and trip): no global counter --
+// (slots from an LDS counter, one LDS atomic per wave and trip: wave_append): no global counter --
 // the cut's bucket may hold millions of scores (R-MAT-22: 7.7 M), and one global
 // atomic per wave on a single address took 12 ms
 __global__ void __launch_bounds__(256) k_compact12(const double *__restrict__ s, int64_t nnz, int64_t chunk,
@@ -180,19 +167,12 @@ __global__ void __launch_bounds__(256) k_compact12(const double *__restrict__ s,
     const uint64_t d = st->prefix >> 52;
     const int64_t b0 = (int64_t)blockIdx.x * chunk;
     const int64_t b1 = b0 + chunk < nnz ? b0 + chunk : nnz;
-    const int lane = threadIdx.x & 63;
     for (int64_t i0 = b0; i0 < b1; i0 += blockDim.x) {  // whole waves run every trip
         const int64_t i = i0 + threadIdx.x;
         const uint64_t k = i < b1 ? order_key(s[i]) : 0ull;
         const bool take = i < b1 && (k >> 52) == d;
-        const unsigned long long m = __ballot(take);
-        if (m) {
-            const int leader = __builtin_ctzll(m);
-            unsigned int base = 0;
-            if (lane == leader) base = atomicAdd(&n_loc, (unsigned int)__popcll(m));
-            base = __shfl(base, leader, 64);
-            if (take) ckey[b0 + base + __popcll(m & ((1ull << lane) - 1ull))] = k;
-        }
+        const unsigned int p = wave_append(take, &n_loc);
+        if (take) ckey[b0 + p] = k;
     }
     __syncthreads();
     if (threadIdx.x == 0) bcount[blockIdx.x] = n_loc;
@@ -243,17 +223,16 @@ __global__ void __launch_bounds__(256) k_ccount(const uint64_t *__restrict__ cke
         b += keep_lowest ? (k < t) : (k > t);
         e += k == t;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        b += __shfl_down(b, off, 64);
-        e += __shfl_down(e, off, 64);
-    }
+    b = wave_sum(b);
+    e = wave_sum(e);
     if ((threadIdx.x & 63) == 0) {
         if (b) atomicAdd(&st->nbeyond_c, b);
         if (e) atomicAdd(&st->ntied, e);
     }
 }
 
-// mask of the strictly-beyond keys; the tie block's indices (unordered) collected
+// mask of the strictly-beyond keys; the tie block's indices (unordered) collected: one
+// global atomic per wave and trip (the cut's bucket may hold millions of scores)
 __global__ void k_mask12(const double *__restrict__ s, int64_t nnz, const Sel12 *__restrict__ st,
                          int keep_lowest, uint8_t *__restrict__ mask, unsigned long long *__restrict__ tcnt,
                          uint64_t *__restrict__ tidx) {
@@ -264,7 +243,7 @@ __global__ void k_mask12(const double *__restrict__ s, int64_t nnz, const Sel12 
         const uint64_t k = i < nnz ? order_key(s[i]) : 0ull;
         if (i < nnz) mask[i] = keep_lowest ? (k < t) : (k > t);
         const bool tie = i < nnz && k == t;
-        const unsigned long long p = wave_slot(tie, tcnt);
+        const unsigned long long p = wave_append(tie, tcnt);
         if (tie) tidx[p] = (uint64_t)i;
     }
 }

@@ -15,8 +15,9 @@
 //            every frontier edge has trussness s + 2
 //   sub-round (k_truss_peel) one wave per frontier edge e1 = (u, v) -- 4 or 16 waves, each
 //            with every 4th or 16th step, while the frontier is short: its lanes stride the
-//            shorter of the two sorted neighbour lists and binary-search the longer; for
-//            every common neighbour w, e2 = (u, w), e3 = (v, w):
+//            shorter of the two sorted neighbour lists and binary-search the longer
+//            (gs_tri.hpp's common_pos, shared with the Simmelian backbone); for every
+//            common neighbour w, e2 = (u, w), e3 = (v, w):
 //              e2 or e3 processed               the triangle is gone already
 //              e2 and e3 in the frontier        nothing is left to decrement
 //              one of them in the frontier      the lower id of the two frontier edges
@@ -24,7 +25,8 @@
 //              neither                          e1 decrements both
 //            so every alive edge loses exactly one per triangle that dies.  A decrement is
 //            one int32 atomicSub; the one that returns s + 1 appends its edge to the next
-//            frontier (once per edge: sup only falls), one append atomic per wave step.
+//            frontier (once per edge: sup only falls), one append atomic per wave step
+//            (gs_wave.hpp's wave_reserve, for the appends of e2 and e3 together).
 //   between  (k_truss_flip) the current frontier becomes processed, the next one current.
 // The state bytes change only between launches; inside a launch other workgroups change
 // sup and the append cursor only, both by atomics, so no kernel reads plain memory that
@@ -43,7 +45,8 @@
 #include <climits>
 #include <cstdlib>
 
-#include "gs_jac.hpp"
+#include "gs_tri.hpp"
+#include "gs_wave.hpp"
 
 namespace gs {
 
@@ -138,7 +141,7 @@ k_truss_min(const uint8_t *__restrict__ state, const int *__restrict__ sup, int6
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < m;
          e += (int64_t)gridDim.x * blockDim.x)
         if (state[e] == kTrussAlive) lo = min(lo, sup[e]);
-    for (int off = 32; off > 0; off >>= 1) lo = min(lo, __shfl_down(lo, off, 64));
+    lo = wave_min(lo);
     if ((threadIdx.x & 63) == 0 && lo != INT_MAX) atomicMax(&ctl->inv, (unsigned int)(INT_MAX - lo));
 }
 
@@ -153,18 +156,15 @@ k_truss_scan(uint8_t *__restrict__ state, const int *__restrict__ sup, int64_t m
     for (int64_t b = blockIdx.x * (int64_t)blockDim.x; b < m; b += (int64_t)gridDim.x * blockDim.x) {
         const int64_t e = b + threadIdx.x;
         const bool in = e < m && state[e] == kTrussAlive && sup[e] <= s;
-        const unsigned long long mk = __ballot(in);
-        if (!mk) continue;
-        unsigned int base = 0;
-        if (lane == 0) base = atomicAdd(&ctl->ncur, (unsigned int)__popcll(mk));
-        base = __shfl(base, 0, 64);
+        if (!__ballot(in)) continue;  // most trips: nothing to list, no steps to add
+        const unsigned int at = wave_append(in, &ctl->ncur);
         unsigned int w = 0;
         if (in) {
-            cur[base + __popcll(mk & ((1ull << lane) - 1ull))] = (int32_t)e;
+            cur[at] = (int32_t)e;
             state[e] = kTrussFrontier;
             w = truss_steps((int32_t)e, eu, ev, ip);
         }
-        for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
+        w = wave_sum(w);
         if (lane == 0) atomicAdd(&ctl->steps, w);
     }
 }
@@ -207,40 +207,23 @@ __device__ __forceinline__ void truss_edge(int32_t f, int s, const int64_t *__re
                                            int *sup, int32_t *next, unsigned int *nnext, int lane,
                                            int32_t sub, int32_t nsub) {
     const int32_t u = eu[f], v = ev[f];
-    const int64_t pu = ip[u], pv = ip[v];
-    const int32_t du = (int32_t)(ip[u + 1] - pu), dv = (int32_t)(ip[v + 1] - pv);
-    const bool ufirst = du <= dv;
-    const int64_t pa = ufirst ? pu : pv, pb = ufirst ? pv : pu;  // a: the shorter list
-    const int32_t da = ufirst ? du : dv, db = ufirst ? dv : du;
-    const int32_t *__restrict__ lb = ix + pb;
-    for (int32_t i0 = sub * 64; i0 < da; i0 += nsub * 64) {  // wave-uniform trips: the ballots are whole
+    const TriRows l(ip, u, v);
+    for (int32_t i0 = sub * 64; i0 < l.da; i0 += nsub * 64) {  // wave-uniform trips: the ballots are whole
         const int32_t i = i0 + lane;
         int32_t d2 = -1, d3 = -1;  // the edges this lane decrements
-        if (i < da) {
-            const int32_t w = ix[pa + i];
-            if (w != u && w != v) {
-                int32_t lo = 0, hi = db;
-                while (lo < hi) {
-                    const int32_t mid = (int32_t)(((uint32_t)lo + (uint32_t)hi) >> 1);
-                    if (lb[mid] < w)
-                        lo = mid + 1;
-                    else
-                        hi = mid;
-                }
-                if (lo < db && lb[lo] == w) {
-                    const int32_t e2 = eid[pa + i], e3 = eid[pb + lo];
-                    const uint8_t s2 = truss_load<TAIL>(state + e2), s3 = truss_load<TAIL>(state + e3);
-                    if (s2 != kTrussDone && s3 != kTrussDone) {
-                        const bool f2 = s2 == kTrussFrontier, f3 = s3 == kTrussFrontier;
-                        if (!f2 && !f3) {
-                            d2 = e2;
-                            d3 = e3;
-                        } else if (f2 && !f3) {
-                            if (f < e2) d3 = e3;
-                        } else if (f3 && !f2) {
-                            if (f < e3) d2 = e2;
-                        }
-                    }
+        const int32_t at = i < l.da ? common_pos(ix, l, u, v, i) : -1;
+        if (at >= 0) {
+            const int32_t e2 = eid[l.pa + i], e3 = eid[l.pb + at];
+            const uint8_t s2 = truss_load<TAIL>(state + e2), s3 = truss_load<TAIL>(state + e3);
+            if (s2 != kTrussDone && s3 != kTrussDone) {
+                const bool f2 = s2 == kTrussFrontier, f3 = s3 == kTrussFrontier;
+                if (!f2 && !f3) {
+                    d2 = e2;
+                    d3 = e3;
+                } else if (f2 && !f3) {
+                    if (f < e2) d3 = e3;
+                } else if (f3 && !f2) {
+                    if (f < e3) d2 = e2;
                 }
             }
         }
@@ -249,12 +232,9 @@ __device__ __forceinline__ void truss_edge(int32_t f, int s, const int64_t *__re
         const unsigned long long m2 = __ballot(a2), m3 = __ballot(a3);
         const unsigned int c2 = (unsigned int)__popcll(m2), c3 = (unsigned int)__popcll(m3);
         if (c2 + c3 == 0) continue;
-        unsigned int base = 0;
-        if (lane == 0) base = atomicAdd(nnext, c2 + c3);
-        base = __shfl(base, 0, 64);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (a2) truss_store<TAIL>(next + base + (unsigned int)__popcll(m2 & below), d2);
-        if (a3) truss_store<TAIL>(next + base + c2 + (unsigned int)__popcll(m3 & below), d3);
+        const unsigned int base = wave_reserve(c2 + c3, nnext);
+        if (a2) truss_store<TAIL>(next + base + lanes_below(m2), d2);
+        if (a3) truss_store<TAIL>(next + base + c2 + lanes_below(m3), d3);
     }
 }
 
@@ -294,7 +274,7 @@ __global__ void k_truss_flip(const int32_t *__restrict__ cur, unsigned int ncur,
         state[e] = kTrussFrontier;
         w += truss_steps(e, eu, ev, ip);
     }
-    for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
+    w = wave_sum(w);
     if ((threadIdx.x & 63) == 0 && w) atomicAdd(&ctl->steps, w);
 }
 
@@ -328,7 +308,7 @@ k_truss_tail(int32_t *la, int32_t *lb, unsigned int ncur, unsigned int steps, un
             truss_store<true>(state + e, kTrussFrontier);
             w += truss_steps(e, eu, ev, ip);
         }
-        for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
+        w = wave_sum(w);
         if (lane == 0 && w) atomicAdd(&n_steps[it & 1u], w);
         ++rounds;
         done += ncur;

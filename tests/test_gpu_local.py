@@ -140,6 +140,28 @@ def test_knobs_change_the_classes_only(eng, monkeypatch, name, knobs):
                         {"short", "stream"} if limits["lmax"] == 8 else {"short", "lds", "stream"})
 
 
+TINY_HUBS = {"one_column": (2, [[0], [1]]),                      # a sort of one item launches nothing
+             "one_source": (3, [[0, 0], [1, 2]]),
+             "unsorted_src": (3, [[1, 0, 1], [0, 1, 2]])}        # two sources, src not ascending
+
+
+@pytest.mark.parametrize("name", list(TINY_HUBS))
+def test_every_segment_a_hub_on_tiny_inputs(eng, monkeypatch, name):
+    """Both class bounds at 0: every segment goes through the gather and the three sorts."""
+    from gsparse.selection import local_filter_scores
+
+    monkeypatch.setenv("GSPARSE_SEGR_SHORT_MAX", "0")
+    monkeypatch.setenv("GSPARSE_SEGR_LDS_MAX", "0")
+    n, ei = TINY_HUBS[name]
+    ei = np.array(ei, dtype=np.int64)
+    E = ei.shape[1]
+    for s in (np.full(E, 0.25), np.arange(E, dtype=np.float64), -np.arange(E, dtype=np.float64)):
+        for keep_lowest in (False, True):
+            _, _, info = check(eng, n, ei, s, local_filter_scores(s, ei, n, keep_lowest), keep_lowest,
+                               smax=0, lmax=0)
+            assert info["classes"]["stream"] == len(set(ei[0].tolist())) and info["classes"]["short"] == 0
+
+
 @pytest.mark.parametrize("name", ["rmat10", "wheel", "hub_pair"])
 def test_two_runs_give_identical_bytes(eng, name):
     n, ei, s, _ = shuffled_case(name, "degsum", False)

@@ -644,6 +644,27 @@ def test_topk_candidate_paths_vs_stable_argsort(gs, monkeypatch):
                         assert nb == beyond and nt == int((s == c).sum()), (mode, frac, low)
 
 
+@pytest.mark.parametrize("E", [1, 63, 64, 65, 129])
+def test_topk_tie_block_with_a_partial_last_wave(gs, E):
+    """Every score equal: the whole input is the tie block, appended one wave at a time, the
+    last wave partly (or, E = 64, just) full; np.argsort(kind='stable') decides the mask."""
+    s = np.full(E, 0.25)
+    ctx = gs._lib.Context()
+    ctx.set_graph_csr(2, np.array([0, 1, 2]), np.array([1, 0], dtype=np.int32), None)
+    eng = gs.engine.Engine(ctx)
+    k = E // 2
+    idx = np.argsort(s, kind="stable")
+    for low in (False, True):
+        mask, cut, nb, nt = eng.topk_mask(s, E, k, low)
+        ref = np.zeros(E, dtype=bool)
+        ref[idx[:k] if low else idx[-k:]] = True  # k = 0: idx[-0:] is every column
+        assert np.array_equal(mask, ref), (E, low)
+        if k > 0:
+            assert (cut, nb, nt) == (0.25, 0, E), (E, low)
+        else:  # E = 1 keeps 0: nothing is selected, so no cut and no tie block
+            assert np.isnan(cut) and nt == 0 and nb == (0 if low else E)
+
+
 def test_edge_cases(gs):
     # isolated nodes, single edge, empty graph, self-loops + duplicates
     for ei, n in [(np.array([[0, 1], [1, 0]]), 5), (np.zeros((2, 0), dtype=np.int64), 3),

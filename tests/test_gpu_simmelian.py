@@ -102,6 +102,22 @@ def test_every_class_is_reached():
     assert _host_classes("rmat10", KNOBS["all_stream"])["stream"] == 12104 // 2
 
 
+@pytest.mark.parametrize("name", ["single_edge", "triangle"])
+def test_smallest_graphs_through_the_stream_class(ctx, name, monkeypatch):
+    """All three bounds at 0: a single edge is one STREAM pair without a hit (one key slot:
+    nothing to sort), a triangle three pairs with one hit each."""
+    eng = _engine(ctx, name)
+    _set_knobs(monkeypatch, KNOBS["all_stream"])
+    pairs = {"single_edge": 1, "triangle": 3}[name]
+    for k0 in (0, 1):
+        want = C.expected(name, k0)[0]
+        got, info = eng.simmelian(k0)
+        assert got.tobytes() == want.tobytes(), (name, k0)
+        assert info["classes"] == {"wave": 0, "mid": 0, "lds": 0, "stream": pairs}
+        assert info["max_common"] == C.max_common(name) == (name == "triangle")
+        assert info["nonzero_pairs"] == (pairs if name == "triangle" else 0)
+
+
 def test_known_answers(ctx):
     got, info = _engine(ctx, "empty").simmelian()
     assert got.shape == (0,) and info == {"max_common": 0, "nonzero_pairs": 0,

@@ -20,10 +20,10 @@
 int main() {
     using namespace gs;
     // a knob can only lower its bound; garbage reads as 0, nothing set as the default
-    EXPECT(sim_limit_text(nullptr, 64) == 64 && sim_limit_text("", 64) == 64);
-    EXPECT(sim_limit_text("7", 64) == 7 && sim_limit_text("64", 64) == 64 && sim_limit_text("65", 64) == 64);
-    EXPECT(sim_limit_text("-3", 64) == 0 && sim_limit_text("x", 64) == 0 && sim_limit_text("0", 64) == 0);
-    EXPECT(sim_limit_text("99999999999999999999", 8192) == 8192);
+    EXPECT(knob_limit(nullptr, 64) == 64 && knob_limit("", 64) == 64);
+    EXPECT(knob_limit("7", 64) == 7 && knob_limit("64", 64) == 64 && knob_limit("65", 64) == 64);
+    EXPECT(knob_limit("-3", 64) == 0 && knob_limit("x", 64) == 0 && knob_limit("0", 64) == 0);
+    EXPECT(knob_limit("99999999999999999999", 8192) == 8192);
     unsetenv("GSPARSE_SIM_WAVE_MAX");
     unsetenv("GSPARSE_SIM_MID_MAX");
     unsetenv("GSPARSE_SIM_LDS_MAX");
@@ -54,8 +54,8 @@ int main() {
                 snprintf(t[0], 16, "%d", wv);
                 snprintf(t[1], 16, "%d", md);
                 snprintf(t[2], 16, "%d", ld);
-                const SimBounds c{sim_limit_text(t[0], kSimWaveMax), sim_limit_text(t[1], kSimMidMax),
-                                  sim_limit_text(t[2], kSimLdsMax)};
+                const SimBounds c{knob_limit(t[0], kSimWaveMax), knob_limit(t[1], kSimMidMax),
+                                  knob_limit(t[2], kSimLdsMax)};
                 for (int64_t d = 1; d <= 10000; ++d) {
                     const int k = sim_class(d, c);
                     EXPECT(k != SIM_WAVE || d <= kSimWaveMax);
