@@ -56,6 +56,22 @@ static constexpr int kPreP = GS_KPRE_P;
 #ifndef GS_PGRP
 #define GS_PGRP 4
 #endif
+// Window form: the p update in one sweep.  A/B hooks for `make variant`, like GS_KPRE and
+// GS_PGRP above; the defaults are what is shipped.  -DGS_P1S=0: the two-pass form of rounds
+// 4-8 (the parent's pass for an A/B on one box).  GS_P1CAP: the last slots whose p_old is
+// requested from the global slot ahead of the sweep (two VGPRs each; 12 leaves the 44-slot
+// kernel without a spilled register, 16 spills 8); slots past the prefix before them go in
+// groups of GS_PGRP.  GS_P1BLK: the sweep's slots per block (one wave-uniform test, the
+// block's LDS reads, its updates; 2 / 4 / 8 measured)
+#ifndef GS_P1S
+#define GS_P1S 1
+#endif
+#ifndef GS_P1CAP
+#define GS_P1CAP 12
+#endif
+#ifndef GS_P1BLK
+#define GS_P1BLK 2
+#endif
 // the one-wave form (k_cg_regres, hand-pipelined gathers) keeps its own, validated
 // distance: at 1 slot its results were wrong (tests m5-narrow, round 3)
 static constexpr int kPreN = 4;

@@ -114,6 +114,10 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
     constexpr bool QS = GS_CG_QS && !QR && !SPLIT;
     // (GS_CG_XG) whole columns in the x-in-Xc form with q stored, not kept in registers
     constexpr bool QSX = GS_CG_XG && QR && !SPLIT;
+    // the p update in one sweep: the window form (a wave is one chunk, its prefix whole
+    // wave-slots).  (The plain two-per-chain form, whose prefix may end inside a wave-slot,
+    // spills two VGPRs at 44 slots with it at any cap and keeps the two-pass update.)
+    constexpr bool P1 = GS_P1S && WIN;
     static_assert(!WIN || (V2 && G == 2 && QS),
                   "the p window: whole columns, unit form, two threads per chain, q stored");
     extern __shared__ double lds[];
@@ -753,10 +757,130 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
                     if (valid(u)) publish(rowof(u), v);
                 }
             };
+            // V2: the slots u < HI past the prefix in groups of GS_PGRP: all their p_old loads (LDS
+            // or the global rows) issued, one wait, then the updates -- one memory round trip
+            // per group instead of one per slot
+            auto pgroups = [&](auto hi_) {
+                constexpr int HI = decltype(hi_)::value;
+                constexpr int kGrp = GS_PGRP > 0 ? GS_PGRP : 1;
+#pragma unroll
+                for (int u0 = 0; u0 < HI; u0 += kGrp) {
+                    if (u0 + kGrp <= ulds) continue;  // wave-uniform: the group is in the prefix
+                    double pog[kGrp];
+#pragma unroll
+                    for (int k = 0; k < kGrp; ++k) {
+                        const int u = u0 + k;
+                        if (u >= HI) break;
+                        const int cd = code_of(rowof(u));
+                        const bool gl = cd >= 0x8000 && u >= ulds && valid(u);
+                        const double lv = spl[cd < 0x8000 ? cd : zslot];
+                        const double gv = __builtin_bit_cast(
+                            double, __builtin_amdgcn_raw_buffer_load_b64(
+                                        prs, gl ? (cd & 0x7fff) * 8 + poff : kOob, 0, kAux));
+                        pog[k] = cd < 0x8000 ? lv : gv;
+                    }
+                    vm_drain();
+#pragma unroll
+                    for (int k = 0; k < kGrp; ++k) {
+                        const int u = u0 + k;
+                        if (u >= HI) break;
+                        if (u >= ulds && valid(u)) {
+                            const double po = pog[k];
+                            if constexpr (!QR) {
+                                const double t1 = alpha_prev * po;
+                                x[u] = x[u] + t1;
+                            }
+                            const double pb = po * beta;
+                            pstore(u, pb + r[u]);
+                        }
+                    }
+                }
+            };
+            // P1: p_old of the tail row's global home, requested with the slots' (below)
+            [[maybe_unused]] double ptg = 0.0;
             if (it == 0) {
 #pragma unroll
                 for (int u = 0; u < R; ++u)
                     if (valid(u)) pstore(u, r[u]);
+            } else if constexpr (P1) {
+                // One sweep.  (a) p_old of the last kCap slots is requested from its home in
+                // the global slot now -- a wave is one chunk and slots u >= ulds hold global
+                // rows in every lane, so no code, LDS read or select: one load each, two
+                // VGPRs held until (c) -- and the tail row's with them.  The loads of slots
+                // inside the prefix (fewer than kCap past it) read stale rows nobody uses.
+                // Slots past the prefix before the last kCap go in groups of GS_PGRP first, as
+                // before (none at Roman size: 11 slots past the prefix).  (b) The slots of
+                // the prefix, LDS to LDS.  The two-pass form ran this pass over all R slots,
+                // the ones past the prefix reading the zero slot: x += fl(alpha * 0.0), a
+                // +-0.0 term, and x starts at +0.0 and is never -0.0 (a sum is -0.0 only when
+                // both terms are), so x + (+-0.0) == x bit for bit and dropping it changes no
+                // bit of x.  (c) The updates of the last kCap slots from (a)'s values, which
+                // arrived under (b): no wait for memory between (a) and the barrier.
+                constexpr int kCap = R < GS_P1CAP ? R : GS_P1CAP;
+                pgroups(std::integral_constant<int, R - kCap>{});
+                launder();
+                double pe[kCap];
+#pragma unroll
+                for (int k = 0; k < kCap; ++k) pe[k] = own_row(rowof(R - kCap + k));
+                {
+                    const int cd = code_of(trow);
+                    ptg = __builtin_bit_cast(
+                        double, __builtin_amdgcn_raw_buffer_load_b64(
+                                    prs, tail && cd >= 0x8000 ? (cd & 0x7fff) * 8 : kOob, 0, kAux));
+                }
+                {
+                    // (b) in blocks of kBlk slots under one wave-uniform test each: a block's
+                    // reads, then its updates.  (A test per slot with the read one slot ahead, or
+                    // leaving the unrolled loop at the first slot past the prefix, gives every
+                    // slot's p_old a register pair of its own across the tests' blocks: 93
+                    // spilled VGPRs at 44 slots.)  In the prefix's last block the slots past it
+                    // read the zero slot and store to the scratch slot, as every slot past the
+                    // prefix did in the two-pass form; fewer than kBlk slots per wave.
+                    const uint32_t zaddr = (uint32_t)zslot * 8u, saddr = (uint32_t)(zslot + 1) * 8u;  // the scratch slot
+                    constexpr int kBlk = GS_P1BLK;
+#pragma unroll
+                    for (int u0 = 0; u0 < R; u0 += kBlk) {
+                        if (u0 < ulds) {  // wave-uniform
+                            double pf[kBlk];
+#pragma unroll
+                            for (int k = 0; k < kBlk; ++k) {
+                                const int u = u0 + k;
+                                if (u < R) pf[k] = lds_at(u < ulds ? lds0() + 256u * G * u : zaddr);
+                            }
+#pragma unroll
+                            for (int k = 0; k < kBlk; ++k) {
+                                const int u = u0 + k;
+                                if (u >= R) break;
+                                const double po = pf[k];
+                                const double t1 = alpha_prev * po;
+                                x[u] = x[u] + t1;
+                                asm volatile("" : "+v"(x[u]));  // now, not deferred past the sweep
+                                const double pb = po * beta;
+                                lds_put(u < ulds && valid(u) ? lds0() + 256u * G * u : saddr, pb + r[u]);
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        }
+                    }
+                }
+                launder();
+#pragma unroll
+                for (int k = 0; k < kCap; ++k) {  // (c)
+                    const int u = R - kCap + k;
+                    if (u >= ulds) {  // wave-uniform
+                        // (a lane past its chain rows, !valid(u), adds whatever the global slot
+                        // holds there -- possibly NaN -- into its x[u], which stayed 0 in the
+                        // two-pass form; its store is dropped.  Harmless only because every read
+                        // of x[u] that reaches memory, the final x below, is under valid(u): an
+                        // unguarded use of x[u] would need a select here)
+                        const double po = pe[k];
+                        const double t1 = alpha_prev * po;
+                        x[u] = x[u] + t1;
+                        const double pb = po * beta;
+                        __builtin_amdgcn_raw_buffer_store_b64(
+                            __builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, pb + r[u]), prs,
+                            valid(u) ? rowof(u) * 8 : kOob, 0, kAux);
+                    }
+                }
             } else {
                 double pb4[R];  // p_old, kPreP slots ahead (each slot reads and writes only its row)
 #pragma unroll
@@ -787,42 +911,7 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
                     }
                     launder();
                     if constexpr (V2 && GS_PGRP > 0) {
-                        // the slots past the prefix in groups of GS_PGRP: all their p_old loads (LDS
-                        // or the global rows) issued, one wait, then the updates -- one memory
-                        // round trip per group instead of one per slot
-                        constexpr int kGrp = GS_PGRP;
-#pragma unroll
-                        for (int u0 = 0; u0 < R; u0 += kGrp) {
-                            if (u0 + kGrp <= ulds) continue;  // wave-uniform: the group is in the prefix
-                            double pog[kGrp > 0 ? kGrp : 1];
-#pragma unroll
-                            for (int k = 0; k < kGrp; ++k) {
-                                const int u = u0 + k;
-                                if (u >= R) break;
-                                const int cd = code_of(rowof(u));
-                                const bool gl = cd >= 0x8000 && u >= ulds && valid(u);
-                                const double lv = spl[cd < 0x8000 ? cd : zslot];
-                                const double gv = __builtin_bit_cast(
-                                    double, __builtin_amdgcn_raw_buffer_load_b64(
-                                                prs, gl ? (cd & 0x7fff) * 8 + poff : kOob, 0, kAux));
-                                pog[k] = cd < 0x8000 ? lv : gv;
-                            }
-                            vm_drain();
-#pragma unroll
-                            for (int k = 0; k < kGrp; ++k) {
-                                const int u = u0 + k;
-                                if (u >= R) break;
-                                if (u >= ulds && valid(u)) {
-                                    const double po = pog[k];
-                                    if constexpr (!QR) {
-                                        const double t1 = alpha_prev * po;
-                                        x[u] = x[u] + t1;
-                                    }
-                                    const double pb = po * beta;
-                                    pstore(u, pb + r[u]);
-                                }
-                            }
-                        }
+                        pgroups(std::integral_constant<int, R>{});
                     } else {
 #pragma unroll
                     for (int u = 0; u < R; ++u) {
@@ -858,7 +947,14 @@ __global__ void __launch_bounds__(kRegThreads) k_cg_regwide(RegArgs A) {
                     stc(code_of(trow), side_r[tix]);
                     publish(trow, side_r[tix]);
                 } else {
-                    const double po = ldc(code_of(trow));
+                    const int tcd = code_of(trow);
+                    double po;
+                    if constexpr (P1) {  // the global home's value arrived with the slots': no round trip here
+                        const double pl = spl[tcd < 0x8000 ? tcd : zslot];
+                        po = tcd < 0x8000 ? pl : ptg;
+                    } else {
+                        po = ldc(tcd);
+                    }
                     if constexpr (!QR) {
                         const double t1 = alpha_prev * po;
                         side_x[tix] = side_x[tix] + t1;
