@@ -84,13 +84,16 @@ __global__ void k_fill_f64(double *p, int64_t n, double v) {
         p[i] = v;
 }
 
-// Validate a caller-provided CSR: sorted, unique, in range.
+// Validate a caller-provided CSR: indptr[0] = 0, both ends of every row inside [0, nnz]
+// and in order (checked before any idx[e] is formed, so a bad indptr reads nothing),
+// columns sorted, unique, in range.
 __global__ void k_check_csr(const int64_t *__restrict__ indptr, const int32_t *__restrict__ idx,
-                            int64_t n, int *__restrict__ bad) {
+                            int64_t n, int64_t nnz, int *__restrict__ bad) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         int64_t a = indptr[i], b = indptr[i + 1];
-        if (b < a) { atomicOr(bad, 1); continue; }
+        if (i == 0 && a != 0) atomicOr(bad, 8);
+        if (a < 0 || b > nnz || b < a) { atomicOr(bad, 1); continue; }
         for (int64_t e = a; e < b; ++e) {
             int32_t v = idx[e];
             if (v < 0 || v >= n) atomicOr(bad, 2);
@@ -222,6 +225,37 @@ void ensure_transpose(gs_ctx *c) {
     g.has_transpose = true;
 }
 
+// What a refused graph call leaves behind: n = nnz = 0 under a new epoch, so no cache and
+// no derived state of the graph before it, and none of the refused arrays, is used again.
+static void set_empty_graph(gs_ctx *c) {
+    Graph &g = c->g;
+    g.n = g.nnz = 0;
+    g.symmetric = 1;
+    ++g.epoch;  // also when the calls below fail
+    g.has_transpose = false;
+    GS_HIP(hipSetDevice(c->device));  // a check before the body's own call may have refused
+    int64_t *ip = (int64_t *)g.indptr.ensure(sizeof(int64_t));
+    GS_HIP(hipMemsetAsync(ip, 0, sizeof(int64_t), c->stream));
+    finish_graph(c);
+}
+
+// Run a graph entry point's body; a refusal leaves the empty graph and keeps its message.
+template <class F>
+static int graph_call(gs_ctx *c, F &&body) {
+    return guard([&] {
+        GS_CHECK(c, GS_EINVAL, "null context");
+        try {
+            body();
+        } catch (...) {
+            try {
+                set_empty_graph(c);
+            } catch (...) {  // the first error is the one reported
+            }
+            throw;
+        }
+    });
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -230,13 +264,11 @@ extern "C" {
 
 int gs_graph_from_edge_index(gs_ctx *c, int64_t n, int64_t E, const int64_t *src,
                              const int64_t *dst, int loc) {
-    return guard([&] {
-        GS_CHECK(c, GS_EINVAL, "null context");
+    return graph_call(c, [&] {
         GS_CHECK(n >= 0 && E >= 0, GS_EINVAL, "negative n/E");
         GS_CHECK(n < (int64_t(1) << 31), GS_EUNSUPPORTED, "n >= 2^31 nodes");
         GS_HIP(hipSetDevice(c->device));
         Graph &g = c->g;
-        g.n = n;
         const int64_t *dsrc = (const int64_t *)to_device(c, c->inbuf, src, sizeof(int64_t) * E, loc);
         const int64_t *ddst = (const int64_t *)to_device(c, c->inbuf2, dst, sizeof(int64_t) * E, loc);
         int *bad = (int *)c->scratch[1].ensure(64);
@@ -270,6 +302,7 @@ int gs_graph_from_edge_index(gs_ctx *c, int64_t n, int64_t E, const int64_t *src
             k_counts<<<grid_for(nnz, 256, 8192), 256, 0, c->stream>>>(start, nnz, E,
                                                                       g.data.as<double>());
         }
+        g.n = n;
         g.nnz = nnz;
         build_indptr_from_rows(c);
         finish_graph(c);
@@ -278,14 +311,11 @@ int gs_graph_from_edge_index(gs_ctx *c, int64_t n, int64_t E, const int64_t *src
 
 int gs_graph_from_csr(gs_ctx *c, int64_t n, int64_t nnz, const int64_t *indptr,
                       const int32_t *indices, const double *data, int loc) {
-    return guard([&] {
-        GS_CHECK(c, GS_EINVAL, "null context");
+    return graph_call(c, [&] {
         GS_CHECK(n >= 0 && nnz >= 0, GS_EINVAL, "negative n/nnz");
         GS_CHECK(n < (int64_t(1) << 31), GS_EUNSUPPORTED, "n >= 2^31 nodes");
         GS_HIP(hipSetDevice(c->device));
         Graph &g = c->g;
-        g.n = n;
-        g.nnz = nnz;
         int64_t *ip = (int64_t *)g.indptr.ensure(sizeof(int64_t) * (n + 1));
         g.indices.ensure(sizeof(int32_t) * (nnz + kIxPad));
         g.data.ensure(sizeof(double) * (nnz ? nnz : 1));
@@ -310,7 +340,7 @@ int gs_graph_from_csr(gs_ctx *c, int64_t n, int64_t nnz, const int64_t *indptr,
         GS_HIP(hipMemsetAsync(bad, 0, sizeof(int), c->stream));
         if (n)
             k_check_csr<<<grid_for(n, 256, 8192), 256, 0, c->stream>>>(ip, g.indices.as<int32_t>(), n,
-                                                                       bad);
+                                                                       nnz, bad);
         int hbad = 0;
         int64_t last = 0;
         GS_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -318,9 +348,13 @@ int gs_graph_from_csr(gs_ctx *c, int64_t n, int64_t nnz, const int64_t *indptr,
         GS_HIP(hipStreamSynchronize(c->stream));
         GS_CHECK(last == nnz, GS_EINVAL, "indptr[n]=%lld != nnz=%lld", (long long)last,
                  (long long)nnz);
-        GS_CHECK(!(hbad & 3), GS_EINVAL, "CSR indices out of range or indptr not monotone");
+        GS_CHECK(!(hbad & 8), GS_EINVAL, "indptr[0] must be 0");
+        GS_CHECK(!(hbad & 3), GS_EINVAL,
+                 "CSR indices out of range, or indptr not monotone inside [0, nnz]");
         GS_CHECK(!(hbad & 4), GS_EUNSUPPORTED,
                  "CSR rows must have sorted, duplicate-free column indices (canonical format)");
+        g.n = n;
+        g.nnz = nnz;
         if (n)
             k_rows_from_indptr<<<grid_for(n, 256, 8192), 256, 0, c->stream>>>(ip, n,
                                                                               g.rows.as<int32_t>());

@@ -77,11 +77,21 @@ int gs_profile_get(gs_ctx *ctx, int i, char *name, int name_len, int64_t *launch
 /* ---- graph --------------------------------------------------------------
  * Replaces GraphSparsifier.__init__'s COO->CSR build (core.py:70-74):
  * sp.csr_matrix((ones(E), (ei[0], ei[1])), (n, n)) -- duplicates summed
- * (data = multiplicity), columns sorted.  Built on the device. */
+ * (data = multiplicity), columns sorted.  Built on the device.
+ * GS_EINVAL: negative n or E, an id outside [0, n); GS_EUNSUPPORTED: n >= 2^31.
+ *
+ * A refused graph call (either entry point, any error code) leaves the EMPTY
+ * graph resident -- gs_graph_shape reports n = nnz = 0 -- under a new graph
+ * epoch: neither the graph set before it, nor anything cached or derived from
+ * it, nor any part of the refused arrays is used by a later call. */
 int gs_graph_from_edge_index(gs_ctx *ctx, int64_t n, int64_t E, const int64_t *src,
                              const int64_t *dst, int loc);
 /* Canonical CSR given directly (sorted columns, no duplicates), e.g. the
- * adj argument of the metrics.py module functions. data may be NULL (=1). */
+ * adj argument of the metrics.py module functions. data may be NULL (=1).
+ * Validated on the device before it becomes the resident graph.  GS_EINVAL:
+ * indptr[0] != 0, indptr[n] != nnz, a row whose ends are not in order inside
+ * [0, nnz] (no index entry of such a row is read), a column outside [0, n);
+ * GS_EUNSUPPORTED: a row with unsorted or duplicate columns, n >= 2^31. */
 int gs_graph_from_csr(gs_ctx *ctx, int64_t n, int64_t nnz, const int64_t *indptr,
                       const int32_t *indices, const double *data, int loc);
 int gs_graph_shape(gs_ctx *ctx, int64_t *n, int64_t *nnz, int *symmetric);
